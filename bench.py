@@ -9,7 +9,20 @@ all-reduce when >1 GPU) at bands=369, 11x11, 200 classes (BASELINE.json metric /
 One process per GPU; per-GPU batch is fixed (weak scaling; 1024 per GPU = 8192 global on 8 GPUs).  Started WITHOUT a
 launcher (`python bench.py --gpus N`, no RANK in the environment) it spawns its own N ranks under torch.distributed.run.
 Synthetic patches (U[0,1), like the reference's min-max-scaled crops) are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line.  `roofline.frac` prices SURVEY.md 8(d)'s per-patch bytes of the conv1 forward (the fp32 input:
+Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, prime and warm up, time the K steps, write the outputs of the last
+timed step when --dump-outputs DIR is given, print the line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...).
+Everything below -- the kernel rooflines timed with HIP events, the steady-state and tile-input medians, the side
+workloads and the CPU baseline -- is measured only with --full.
+
+--dump-outputs DIR: what the K timed steps' last step hands its caller, as DIR/loss.npy, DIR/logits.npy (float32 (B, 200)),
+DIR/parameters.npy and DIR/buffers.npy (float64: the model's parameters / floating-point buffers after the step, flattened
+and concatenated in named_parameters() / named_buffers() order).  The priming steps run for a fixed time, not a fixed
+count, so with --dump-outputs the model and Adam state they moved are put back before the warm-up steps: the outputs then
+depend on the arguments alone and two builds can be compared output for output.
+
+With --full: `roofline.frac` prices SURVEY.md 8(d)'s per-patch bytes of the conv1 forward (the fp32 input:
 182.9 MB per launch at B = 1024); with the half output: `frac_with_output`; with the bf16 tile by-product too: `frac_with_byproduct`.  The one-GPU line also carries, timed
 after the contract's region (20 steps each): `fp32` (the reference's own precision), `ensemble24` (BASELINE configs[4]), `metadata` (BASELINE configs[3]),
 `multistage` (the reference's train.py path: 5 levels x 3 years, one launch chain vs level by level) and `module_path` (the unchanged reference step on the plugin modules with optim.DtaAdam / optim.cross_entropy).  Inside the timed loop the two first-conv kernels are timed with HIP events recorded on their own
@@ -83,7 +96,37 @@ def parse():
                     help="inside the contract's timed steps the reported kernel is event-timed on every Nth step only (an "
                          "event pair costs ~5 us of stream time; measured: 11.6 us per step with a pair on every step)")
     ap.add_argument("--traffic-file", default=None, help="profiles/*_traffic_step.json whose PMC counters are quoted")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the first-conv rooflines (HIP events inside and "
+                         "after the timed steps), the steady-state and tile-input medians, the side workloads and the CPU "
+                         "baseline (the options above that configure them act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (see the module docstring)")
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMENTS = 1 << 22     # per dumped array (<= 32 MB as float64); a larger one is written as a fixed, seeded sample
+
+
+def capture_outputs(model, loss, logits):
+    """Device copies of what the step that just finished hands its caller, taken before any later step overwrites the
+    trainer's loss / logits buffers."""
+    with torch.no_grad():
+        params = [p.detach().reshape(-1).to(torch.float64) for _, p in model.named_parameters()]
+        bufs = [b.detach().reshape(-1).to(torch.float64) for _, b in model.named_buffers() if b.is_floating_point()]
+        return {"loss": loss.detach().to(torch.float32).clone(), "logits": logits.detach().to(torch.float32).clone(),
+                "parameters": torch.cat(params), "buffers": torch.cat(bufs) if bufs else torch.zeros(0, dtype=torch.float64)}
+
+
+def dump_outputs(outs, d):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in outs.items():
+        arr = t.cpu().numpy()
+        if arr.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, DUMP_MAX_ELEMENTS, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def cpu_baseline(batch, seconds):
@@ -451,6 +494,8 @@ def side_module_path(a, dev, fused_ms, steps=20):
 def main():
     a = parse()
     if a.workload == "ensemble24":
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs: the hang2020 workload only")
         if not torch.cuda.is_available():
             raise SystemExit("bench.py needs a ROCm GPU (the HIP path has no CPU fallback)")
         return main_ensemble24(a)
@@ -591,6 +636,11 @@ def main():
         if dist_on:
             torch.distributed.barrier()
 
+    # --dump-outputs: the priming steps run for a fixed time, so their count differs from run to run; the state they move is
+    # put back afterwards, and the outputs of the timed steps depend on the arguments alone
+    init_state = None
+    if a.dump_outputs:
+        init_state = ({k: v.detach().clone() for k, v in trainer.model.state_dict().items()}, trainer.optimizer_state_dict())
     primed = 0
     t_prime = time.perf_counter()
     while a.prime_seconds > 0:
@@ -605,15 +655,20 @@ def main():
             stop = flag.item() > 0.0
         if stop:
             break
+    if init_state is not None:
+        torch.cuda.synchronize()
+        trainer.model.load_state_dict(init_state[0])
+        trainer.load_optimizer_state_dict(init_state[1])
+        del init_state
     for i in range(a.warmup):
         trainer.train_step(xs[i % nb], ys[i % nb])
     torch.cuda.synchronize()
     barrier()
-    # the kernel reported as `roofline` is timed inside the contract's region (one HIP-event pair per step, measured
+    # --full: the kernel reported as `roofline` is timed inside the contract's region (one HIP-event pair per step, measured
     # cost 4-5 us per step and pair); the other first-conv kernel over further steps of the same run, so that the timed
     # region carries one pair, not two
     other = "wgrad0" if a.site == "fwd0" else "fwd0"
-    if rank == 0:
+    if rank == 0 and a.full:
         L.dta_profile_set_stride(max(1, a.site_stride))
         L.dta_profile_enable(SITE[a.site])
     torch.cuda.synchronize()
@@ -625,6 +680,8 @@ def main():
     barrier()
     el = time.perf_counter() - t0
     trainer.check_exchange()                 # a peer-exchange step that timed out waiting for a rank raises here
+    if a.dump_outputs and rank == 0:
+        dump_outputs(capture_outputs(trainer.model, loss, trainer.logits), a.dump_outputs)
     rank_ms = {"min": round(el_own / a.steps * 1e3, 4), "max": round(el_own / a.steps * 1e3, 4)}
     if dist_on:
         t = torch.tensor([el, el_own, -el_own], dtype=torch.float64, device=dev)
@@ -637,24 +694,26 @@ def main():
         buf = (C.c_float * 512)()
         n = L.dta_profile_collect_site(site, buf, 512)
         return [buf[i] for i in range(max(n, 0))]
-    site_ms = {a.site: collect(SITE[a.site])} if rank == 0 else {}
-    if rank == 0:
-        L.dta_profile_enable(-1)
-        L.dta_profile_set_stride(1)
-    n_other = min(a.steps, 50) if a.other_steps is None else a.other_steps
-    if rank == 0:
-        L.dta_profile_enable(SITE[other])
-    for i in range(n_other):                 # (every rank: the steps issue the collectives)
-        trainer.train_step(xs[i % nb], ys[i % nb])
-    torch.cuda.synchronize()
-    barrier()
-    if rank == 0:
-        site_ms[other] = collect(SITE[other])
-        L.dta_profile_enable(-1)
+    site_ms, n_other = {}, 0
+    if a.full:
+        site_ms = {a.site: collect(SITE[a.site])} if rank == 0 else {}
+        if rank == 0:
+            L.dta_profile_enable(-1)
+            L.dta_profile_set_stride(1)
+        n_other = min(a.steps, 50) if a.other_steps is None else a.other_steps
+        if rank == 0:
+            L.dta_profile_enable(SITE[other])
+        for i in range(n_other):                 # (every rank: the steps issue the collectives)
+            trainer.train_step(xs[i % nb], ys[i % nb])
+        torch.cuda.synchronize()
+        barrier()
+        if rank == 0:
+            site_ms[other] = collect(SITE[other])
+            L.dta_profile_enable(-1)
 
-    # steady state beyond the contract's K steps: each step bracketed by its own HIP events (no host sync in between)
+    # --full: steady state beyond the contract's K steps: each step bracketed by its own HIP events (no host sync in between)
     steady = None
-    if a.steady_steps > 0:
+    if a.full and a.steady_steps > 0:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steady_steps)]
         for i, (e0, e1) in enumerate(evs):
             e0.record()
@@ -672,7 +731,7 @@ def main():
     # SURVEY 8 row n2): the first conv then reads 2 bytes per value and writes no tile by-product.  A side number: the
     # headline above keeps the reference's input format (fp32 NCHW).
     tile_in = None
-    if a.tile_steps > 0 and a.precision == "bf16" and not dist_on:      # (single process only: the steps would issue collectives)
+    if a.full and a.tile_steps > 0 and a.precision == "bf16" and not dist_on:      # (single process only: the steps would issue collectives)
         from deeptreeattention_amd.preprocess import PatchTiles
         nchunk = (BANDS + 15) // 16
 
@@ -800,7 +859,10 @@ def main():
             "steady_state": steady,
             "tile_input": tile_in,
         }
-        if world == 1 and not dist_on and not a.no_side:
+        if not a.full:      # the kernel rooflines and the medians beyond the K steps are measured with --full only
+            for k in ("roofline", "roofline_mfma", "roofline_hbm", "steady_state", "tile_input"):
+                out.pop(k, None)
+        if a.full and world == 1 and not dist_on and not a.no_side:
             # side workloads, driver-timed in the same run AFTER the contract's region (20 steps each): the reference's own
             # precision, BASELINE configs[4], and the unchanged-reference-step plugin path
             fused_ms = steady["median_ms_per_step"] if steady else el / a.steps * 1e3
@@ -817,7 +879,7 @@ def main():
                 except Exception as e:      # noqa: BLE001 -- a side number must never cost the headline line
                     out[name] = {"error": f"{type(e).__name__}: {e}"[:300]}
             trainer = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_batch, a.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dist_on:

@@ -115,14 +115,47 @@ def bf16_yardstick(golden):
     return Bf16Yardstick(golden("bf16_autocast.npz"))
 
 
+_devlib_run = None
+
+
+def devlib_child_run():
+    """ONE child pytest process per session that loads the developer library (DTA_DEV_LIB=1: libdta_hip_dev.so, the same
+    sources compiled with -DDTA_DEV_SWITCHES) and runs every `devlib` test of tests/test_kernel_variants_gpu.py and
+    tests/test_hip_parity.py.  Returns (CompletedProcess, {node id: PASSED / FAILED / ERROR / ...})."""
+    global _devlib_run
+    if _devlib_run is None:
+        import subprocess
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-rA", "-m", "gpu and devlib", "-p", "no:cacheprovider",
+                            os.path.join(REPO, "tests", "test_kernel_variants_gpu.py"), os.path.join(REPO, "tests", "test_hip_parity.py")],
+                           cwd=REPO, env=dict(os.environ, DTA_DEV_LIB="1"), capture_output=True, text=True)
+        outcomes = {}
+        for line in r.stdout.splitlines():
+            word, _, rest = line.partition(" ")
+            if word in ("PASSED", "FAILED", "ERROR", "XFAIL", "XPASS"):
+                outcomes[rest.split(" - ")[0].strip()] = word
+        _devlib_run = (r, outcomes)
+    return _devlib_run
+
+
+@pytest.hookimpl(tryfirst=True)
+def pytest_pyfunc_call(pyfuncitem):
+    """A `devlib` test flips a developer switch, which only the developer library reads: the product library reads nothing
+    from the environment.  In a process that loaded the product library the test's body runs in devlib_child_run()'s
+    process instead, and the test passes or fails with what it did there."""
+    if pyfuncitem.get_closest_marker("devlib") is None:
+        return None
+    from deeptreeattention_amd import _lib
+    if _lib.lib().dta_dev_switches_enabled():
+        return None                       # the developer library is loaded here: the body runs in this process
+    r, outcomes = devlib_child_run()
+    got = outcomes.get(pyfuncitem.nodeid)
+    assert got == "PASSED", (pyfuncitem.nodeid, got, r.stdout[-3000:] + r.stderr[-1000:])
+    return True
+
+
 @pytest.fixture
 def devlib():
-    """Tests that flip a developer switch (alternative launch plans) need the DEVELOPER library: the product library reads
-    nothing from the environment.  In a default run they are skipped here and executed by
-    tests/test_kernel_variants_gpu.py::test_developer_switch_variants_in_the_developer_library, which re-runs them in a
-    process that loads libdta_hip_dev.so (DTA_DEV_LIB=1)."""
+    """The library handle of a test that flips a developer switch (alternative launch plans).  In the product library's
+    process such a test's body runs in the developer library's process (pytest_pyfunc_call above)."""
     from deeptreeattention_amd import _lib
-    L = _lib.lib()
-    if not L.dta_dev_switches_enabled():
-        pytest.skip("developer-switch variant: runs in libdta_hip_dev.so (test_developer_switch_variants_in_the_developer_library)")
-    return L
+    return _lib.lib()

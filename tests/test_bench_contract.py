@@ -1,5 +1,6 @@
-"""The bench.py output contract: ONE JSON line with the driver's keys plus the `roofline` and `cpu_baseline` objects.
-CPU: the committed artifact under profiles/ has the full schema.  GPU: a short live run prints a conforming line."""
+"""The bench.py output contract: ONE JSON line with the driver's keys; with --full also the `roofline` and `cpu_baseline`
+objects.  CPU: the committed artifact under profiles/ has the full schema.  GPU: a short live run prints a conforming line,
+and a plain run measures the headline only and writes the outputs of its last timed step on request."""
 import json
 import os
 import subprocess
@@ -31,6 +32,13 @@ def _check(line, want_cpu):
     return d
 
 
+def test_bench_offers_full_and_dump_outputs():
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=120, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
 @pytest.mark.parametrize("name", ["r01_bench_bf16_default.json", "r02_bench_bf16_default.json"])
 def test_committed_bench_artifact_has_the_contract_schema(name):
     d = _check(open(os.path.join(REPO, "profiles", name)).read(), True)
@@ -44,7 +52,7 @@ def test_committed_bench_artifact_has_the_contract_schema(name):
 @pytest.mark.gpu
 def test_bench_prints_one_conforming_json_line():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2", "--site-stride", "2",
-                          "--no-cpu-baseline", "--no-side"], capture_output=True, text=True, timeout=240, cwd=REPO)
+                          "--no-cpu-baseline", "--no-side", "--full"], capture_output=True, text=True, timeout=240, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1
@@ -57,6 +65,38 @@ def test_bench_prints_one_conforming_json_line():
     assert abs(sr["frac"] - sr["achieved"] / sr["peak"]) < 1e-3 and sr["algorithmic_flop_per_patch"] == 154486824
     ss = d["steady_state"]
     assert ss["steps"] >= 200 and 0.5 * d["ms_per_step"] < ss["median_ms_per_step"] < 2 * d["ms_per_step"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run measures the headline only (no kernel rooflines, medians, side workloads or CPU baseline) and, with
+    --dump-outputs, writes the last timed step's loss, scores, parameters and buffers.  Two runs with the same arguments
+    write the same bits, although their time-bounded priming ran different numbers of steps."""
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                              "--batch", "128", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=240, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["unit"] == "patches/s" and line["dtype"] == "bf16"
+        assert abs(line["value"] - 3 * 128 / (line["ms_per_step"] * 1e-3 * 3)) < 1e-3 * line["value"]
+        for k in ("roofline", "roofline_mfma", "steady_state", "tile_input", "cpu_baseline", "fp32", "ensemble24", "metadata",
+                  "multistage", "module_path"):
+            assert k not in line, k
+        got = {n: np.load(d / (n + ".npy")) for n in ("loss", "logits", "parameters", "buffers")}
+        assert got["loss"].shape == () and got["loss"].dtype == np.float32
+        assert abs(float(got["loss"]) - line["final_loss"]) <= 1e-5 * max(1.0, abs(line["final_loss"]))
+        assert got["logits"].shape == (128, 200) and got["logits"].dtype == np.float32
+        assert got["parameters"].dtype == np.float64 and got["parameters"].size > 900_000
+        assert got["buffers"].dtype == np.float64 and got["buffers"].size > 0
+        assert all(np.isfinite(v).all() for v in got.values())
+        dumps.append(got)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 @pytest.mark.gpu
@@ -103,10 +143,10 @@ def test_plain_bench_gpus_2_spawns_its_own_ranks():
 
 @pytest.mark.gpu
 def test_default_bench_line_carries_the_side_workloads():
-    """The one-GPU driver line times, after the contract's region, the reference's own precision (fp32), BASELINE
+    """The one-GPU --full line times, after the contract's region, the reference's own precision (fp32), BASELINE
     configs[4] (ensemble24) and the unchanged-reference-step plugin path (module_path), 20 steps each."""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2", "--steady-steps", "20",
-                          "--tile-steps", "0", "--no-cpu-baseline", "--prime-seconds", "0.2"], capture_output=True, text=True,
+                          "--tile-steps", "0", "--no-cpu-baseline", "--prime-seconds", "0.2", "--full"], capture_output=True, text=True,
                          timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -150,11 +190,22 @@ def test_plain_bench_gpus_8_spawns_eight_ranks():
     bench.py spawns its eight ranks itself, they share the test box's one GPU (development mode: never a measured
     configuration), rendezvous on 127.0.0.1, choose the exchange collectively (the peer exchange: its probe passes between
     processes of one device), run the overlapped step at the REAL 369-band / 200-class flat layout with 8 shards, and rank 0
-    prints exactly one JSON line whose process group spanned 8 ranks."""
+    prints exactly one JSON line whose process group spanned 8 ranks.
+    The collective choice is split in two so that no more than nine processes hold the device at once (eight ranks that
+    each start their probe would be sixteen, plus this one): the test runs the eight-rank probe itself first -- it must
+    pass, which is what makes the default choice the peer exchange -- and the ranks then take that exchange as given."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        probes = [subprocess.Popen([sys.executable, os.path.join(REPO, "deeptreeattention_amd", "peer_probe.py"), d, str(r), "8", "0"],
+                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(8)]
+        outs = [p.communicate(timeout=300) for p in probes]
+    for p, (so, se) in zip(probes, outs):
+        assert p.returncode == 0, se[-2000:]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(DTA_BENCH_BACKEND="gloo", GLOO_SOCKET_IFNAME="lo")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                          "--batch", "32", "--steady-steps", "0"], capture_output=True, text=True, timeout=900, cwd=REPO, env=env)
+                          "--batch", "32", "--steady-steps", "0", "--exchange", "peer"], capture_output=True, text=True,
+                         timeout=900, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

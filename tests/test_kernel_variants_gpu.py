@@ -13,7 +13,7 @@ import sys
 import pytest
 import torch
 
-from conftest import rel_l2
+from conftest import devlib_child_run, rel_l2
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,8 +22,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_developer_switch_variants_in_the_developer_library():
     """Every test marked `devlib` (this file and tests/test_hip_parity.py) compares an alternative launch plan, selected by
     a developer switch, with the default plan.  The product library has no switches (it reads nothing from the environment),
-    so those tests are skipped in this process and run HERE, in a process that loads libdta_hip_dev.so: the same sources
-    compiled with -DDTA_DEV_SWITCHES (same dta_build_id)."""
+    so their bodies run in ONE process that loads libdta_hip_dev.so -- the same sources compiled with -DDTA_DEV_SWITCHES (same
+    dta_build_id) -- and each of them passes or fails here with what it did there (conftest.devlib_child_run)."""
     from deeptreeattention_amd import _lib
     L = _lib.lib()
     if L.dta_dev_switches_enabled():
@@ -35,9 +35,7 @@ def test_developer_switch_variants_in_the_developer_library():
     assert probe.returncode == 0, probe.stderr[-2000:]
     enabled, build_id = probe.stdout.split()
     assert enabled == "1" and build_id == L.dta_build_id().decode(), (probe.stdout, "libdta_hip_dev.so is stale: python -m deeptreeattention_amd.build")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu and devlib", "-p", "no:cacheprovider",
-                        os.path.join(REPO, "tests", "test_kernel_variants_gpu.py"), os.path.join(REPO, "tests", "test_hip_parity.py")],
-                       cwd=REPO, env=env, capture_output=True, text=True)
+    r, _ = devlib_child_run()
     tail = r.stdout[-3000:] + r.stderr[-1000:]
     assert r.returncode == 0, tail
     assert " passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], tail

@@ -10,6 +10,21 @@ from conftest import rel_l2
 TOL = 2e-5  # fp64 oracle vs the reference's fp32 torch run
 
 
+@pytest.fixture(autouse=True)
+def _native_cpu_convolutions():
+    """The torch restatement runs here on torch's own CPU convolutions, not oneDNN's.  oneDNN picks its kernels by host
+    (instruction set, thread count), and what it returns for the spatial attention's single-channel convolutions differs
+    from host to host by more than the golden tolerances, up to non-finite gradients.  The native path holds them on every
+    instruction set and thread count tried.  (bench.py's cpu_baseline keeps oneDNN: it times the reference's own setup.)"""
+    import torch
+    was = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False
+    try:
+        yield
+    finally:
+        torch.backends.mkldnn.enabled = was
+
+
 def sample_idx(n, count=256):
     return (prng.hash_u64(7, 99, count) % np.uint64(n)).astype(np.int64)
 
@@ -239,6 +254,46 @@ def _ensemble_step_inputs(step, years, B, bands, classes):
     return imgs, prng.randint(82 + step, 7, (B,), classes)
 
 
+ADAM_RATIO_BOUND = 1.011      # max |m_hat| / sqrt(v_hat) over Adam's first five steps at betas (0.9, 0.999)
+
+
+def _pnorm_tolerance(p, p0, k, ref, lr, steps):
+    """How far a parameter's norm may lie from the reference's after `steps` Adam steps from the same initial values.
+    Every tensor: 1e-5 of the norm.  A conv bias feeds batch-statistics BatchNorm, so its gradient is analytically zero
+    (_check_noise_gradients) and what a run computes is rounding noise of the host's CPU kernels (instruction set, thread
+    count); Adam turns that noise into steps of up to lr * ADAM_RATIO_BOUND per element in a direction the noise picks.
+    The reference's own bias is therefore known only to within that reach of the initial values:
+    | ||p|| - ||p_ref|| | <= ||p - p0|| + ||p_ref - p0||."""
+    tol = 1e-5 * ref
+    if k.endswith("conv_layer.bias"):
+        a = p[k].detach().numpy().astype(np.float64)
+        reach = np.sqrt(((a - p0[k].numpy().astype(np.float64)) ** 2).sum())
+        tol += reach + lr * ADAM_RATIO_BOUND * steps * np.sqrt(a.size)
+    return tol
+
+
+def _buffer_tolerance(p, k, ref, lr, steps, momentum=0.1):
+    """rel-L2 tolerance of a BatchNorm buffer against the reference's after `steps` training-mode forwards: 1e-4.  The
+    running mean of a BatchNorm that follows a conv also averages that conv's bias, which two hosts move apart by up to
+    2 lr ADAM_RATIO_BOUND per element and Adam step (_pnorm_tolerance): the forwards so far saw biases at most steps - 1
+    Adam steps from their initial values, and the running mean holds 1 - (1 - momentum)^steps of what they contributed."""
+    tol = 1e-4
+    if k.endswith("bn1.running_mean"):
+        bias = k[:-len("bn1.running_mean")] + "conv_layer.bias"
+        if bias in p:
+            reach = 2 * lr * ADAM_RATIO_BOUND * (steps - 1) * np.sqrt(p[bias].numel())
+            tol += (1 - (1 - momentum) ** steps) * reach / np.linalg.norm(np.asarray(ref, np.float64))
+    return tol
+
+
+def _check_noise_gradients(p):
+    """The premise of _pnorm_tolerance: every conv bias's gradient is rounding noise next to its conv weight's."""
+    for k, t in p.items():
+        if k.endswith("conv_layer.bias") and t.grad is not None:
+            gw = p[k[:-len("bias")] + "weight"].grad
+            assert float(t.grad.norm()) <= 1e-5 * float(gw.norm()), (k, float(t.grad.norm()), float(gw.norm()))
+
+
 def test_torch_oracle_ensemble_steps_match_reference_golden(golden):
     """Year-ensemble train steps (MultiStage recipe) incl. two steps with an all-zero year: the torch restatement
     against the reference's learned_ensemble + F.cross_entropy + Adam."""
@@ -247,6 +302,7 @@ def test_torch_oracle_ensemble_steps_match_reference_golden(golden):
     g = golden("ensemble_steps.npz")
     years, bands, classes, B, lr = 3, 16, 7, 6, 1e-3
     p = OT.to_tensors(O.init_params(O.learned_ensemble_spec(years, bands, classes), seed=81))
+    p0 = {k: t.detach().clone() for k, t in p.items()}
     w = torch.from_numpy((0.1 + (np.arange(classes) % 7)).astype(np.float32))
     step_fn = OT.EnsembleTrainStep(p, lr, w)
     for step in range(4):
@@ -254,13 +310,15 @@ def test_torch_oracle_ensemble_steps_match_reference_golden(golden):
         s, loss = step_fn([torch.from_numpy(a) for a in imgs], torch.from_numpy(y))
         assert rel_l2(s.numpy(), g[f"step{step}/score"]) < 1e-4, step
         assert abs(float(loss) - float(g[f"step{step}/loss"])) < 1e-4 * abs(float(g[f"step{step}/loss"]))
+        _check_noise_gradients(p)
         for k, t in p.items():
             if not t.requires_grad:
-                assert rel_l2(t.numpy(), g[f"step{step}/buf/{k}"]) < 1e-4, (step, k)
+                ref = g[f"step{step}/buf/{k}"]
+                assert rel_l2(t.numpy(), ref) < _buffer_tolerance(p, k, ref, lr, step + 1), (step, k)
                 continue
             a = t.detach().numpy()
-            assert abs(np.sqrt((a.astype(np.float64) ** 2).sum()) - float(g[f"step{step}/pnorm/{k}"])) \
-                <= 1e-5 * float(g[f"step{step}/pnorm/{k}"]), (step, k)
+            ref = float(g[f"step{step}/pnorm/{k}"])
+            assert abs(np.sqrt((a.astype(np.float64) ** 2).sum()) - ref) <= _pnorm_tolerance(p, p0, k, ref, lr, step + 1), (step, k)
 
 
 def test_torch_oracle_multistage_steps_match_reference_golden(golden):
@@ -274,21 +332,25 @@ def test_torch_oracle_multistage_steps_match_reference_golden(golden):
     steps = []
     for l, classes in enumerate(c["classes"]):
         p = OT.to_tensors(O.init_params(O.learned_ensemble_spec(c["years"], c["bands"], classes), seed=301 + l))
-        steps.append((p, OT.EnsembleTrainStep(p, c["lrs"][l], torch.from_numpy(multistage_weight(classes)))))
+        p0 = {k: t.detach().clone() for k, t in p.items()}
+        steps.append((p, p0, OT.EnsembleTrainStep(p, c["lrs"][l], torch.from_numpy(multistage_weight(classes)))))
     for step in range(c["steps"]):
-        for l, (p, fn) in enumerate(steps):
+        for l, (p, p0, fn) in enumerate(steps):
             imgs, y = multistage_inputs(step, l, c["years"], c["B"], c["bands"], c["classes"][l])
             s, loss = fn([torch.from_numpy(a) for a in imgs], torch.from_numpy(y))
             tag = f"step{step}/level{l}"
             assert rel_l2(s.numpy(), g[f"{tag}/score"]) < 1e-4, tag
             assert abs(float(loss) - float(g[f"{tag}/loss"])) < 1e-4 * abs(float(g[f"{tag}/loss"])), tag
+            _check_noise_gradients(p)
             for k, t in p.items():
                 if not t.requires_grad:
-                    assert rel_l2(t.numpy(), g[f"{tag}/buf/{k}"]) < 1e-4, (tag, k)
+                    ref = g[f"{tag}/buf/{k}"]
+                    assert rel_l2(t.numpy(), ref) < _buffer_tolerance(p, k, ref, c["lrs"][l], step + 1), (tag, k)
                     continue
                 a = t.detach().numpy()
                 ref = float(g[f"{tag}/pnorm/{k}"])
-                assert abs(np.sqrt((a.astype(np.float64) ** 2).sum()) - ref) <= 1e-5 * ref, (tag, k)
+                tol = _pnorm_tolerance(p, p0, k, ref, c["lrs"][l], step + 1)
+                assert abs(np.sqrt((a.astype(np.float64) ** 2).sum()) - ref) <= tol, (tag, k)
 
 
 def _metadata_params(g, bands, classes):

@@ -120,7 +120,7 @@ def test_bench_runs_on_rccl_backend_with_one_rank():
     env = dict(os.environ, DTA_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29549", RANK="0",
                LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--steady-steps", "20", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                        "--steady-steps", "20", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

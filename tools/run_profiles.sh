@@ -3,8 +3,8 @@
 # summary can be re-derived from files that are kept.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --site wgrad0 --no-cpu-baseline --no-side > $O/bench_wgrad0.json 2>> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --site wgrad0 --no-cpu-baseline --no-side > $O/bench_wgrad0.json 2>> $O/bench_default.err
 python bench.py --workload ensemble24 --steps 100 --warmup 10 > $O/bench_ensemble24.json 2>> $O/bench_default.err
 python bench.py --workload ensemble24 --steps 100 --warmup 10 --site wgrad0 > $O/bench_ensemble24_wgrad0.json 2>> $O/bench_default.err
 bash tools/dp_probe.sh > $O/dp_one_rank.txt 2>> $O/bench_default.err
