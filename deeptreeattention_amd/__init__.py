@@ -4,9 +4,11 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.Hang2020   <->  src/models/Hang2020.py
     deeptreeattention_amd.year       <->  src/models/year.py        (learned_ensemble)
     deeptreeattention_amd.engine     fused train step (forward + weighted CE + backward + Adam, optional RCCL DDP)
+    deeptreeattention_amd.hierarchy  <->  src/models/multi_stage.py:368-485 (the levels' predictions -> one species label)
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.
 """
 from . import Hang2020  # noqa: F401
 from .Hang2020 import set_default_precision, get_default_precision  # noqa: F401
+from .hierarchy import Hierarchy, scores_from_confusion  # noqa: F401
 
-__all__ = ["Hang2020", "set_default_precision", "get_default_precision"]
+__all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion"]

@@ -80,6 +80,10 @@ class Level(C.Structure):           # dta_level
 MAX_LEVELS = 8   # DTA_MAX_LEVELS
 
 
+class HierarchyTable(C.Structure):  # dta_hierarchy
+    _fields_ = [("levels", C.c_int), ("n_species", C.c_int), ("classes", C.c_int * MAX_LEVELS), ("table", C.c_void_p)]
+
+
 ADAM_MAX_SEGMENTS = 16   # DTA_ADAM_MAX_SEGMENTS
 
 
@@ -182,6 +186,14 @@ def lib():
         L.dta_multistage_predict.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams),
                                              C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+        L.dta_multistage_predict_ensemble.restype = C.c_int
+        L.dta_multistage_predict_ensemble.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams),
+                                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(HierarchyTable),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dta_hierarchy_resolve.restype = C.c_int
+        L.dta_hierarchy_resolve.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(HierarchyTable),
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dta_multistage_backward.restype = C.c_int
         L.dta_multistage_backward.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams), C.c_void_p,
                                               C.POINTER(SubnetGrads), C.c_void_p, C.c_void_p]

@@ -1267,6 +1267,76 @@ int dta_multistage_predict(const dta_net_desc* d, int levels, const dta_level* l
   return launch_softmax_top2_multi(m, st);
 }
 
+// the hierarchy arguments of the two ensemble-label calls, checked on the host before anything is launched
+static int hierarchy_args(const char* who, int levels, const dta_hierarchy* h, long long* ens_label, float* ens_score, int* ens_level,
+                          const long long* labels, long long* confusion, HierarchyArgs* e) {
+  if (!h || !h->table) { dta_set_error("%s: null hierarchy table", who); return 1; }
+  if (!ens_label || !ens_score || !ens_level) { dta_set_error("%s: null ensemble output", who); return 1; }
+  if ((labels != nullptr) != (confusion != nullptr)) { dta_set_error("%s: labels and confusion come together or not at all", who); return 1; }
+  if (h->levels < 1 || h->levels > DTA_MAX_LEVELS || h->levels != levels) {
+    dta_set_error("%s: the hierarchy table has %d levels, the call %d", who, h->levels, levels); return 1;
+  }
+  if (h->n_species < 1) { dta_set_error("%s: the hierarchy table has %d species", who, h->n_species); return 1; }
+  memset(e, 0, sizeof(*e));
+  for (int l = 0; l < levels; ++l) {
+    if (h->classes[l] < 1) { dta_set_error("%s: the hierarchy table's level %d has %d classes", who, l, h->classes[l]); return 1; }
+    e->off[l + 1] = e->off[l] + h->classes[l];
+  }
+  for (int l = levels; l < BLEND_CE_MULTI_MAX; ++l) e->off[l + 1] = e->off[l];
+  e->next = h->table + levels + 1; e->species = e->next + e->off[levels]; e->n_species = h->n_species;
+  e->ens_label = ens_label; e->ens_score = ens_score; e->ens_level = ens_level; e->labels = labels; e->confusion = confusion;
+  return 0;
+}
+
+int dta_multistage_predict_ensemble(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
+                                    const float* const* x, const float* gate, void* workspace, float* const* probs,
+                                    long long* const* top_idx, float* const* top_score, const dta_hierarchy* table,
+                                    long long* ens_label, float* ens_score, int* ens_level, const long long* labels,
+                                    long long* confusion, void* stream) {
+  Plan p; dta_net_desc dd; HierarchyArgs e;
+  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("dta_multistage_predict_ensemble: null argument"); return 1; }
+  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_predict_ensemble")) return 1;
+  if (hierarchy_args("dta_multistage_predict_ensemble", levels, table, ens_label, ens_score, ens_level, labels, confusion, &e)) return 1;
+  for (int l = 0; l < levels; ++l)
+    if (lv[l].classes != table->classes[l]) {
+      dta_set_error("dta_multistage_predict_ensemble: level %d has %d classes, the hierarchy table %d", l, lv[l].classes, table->classes[l]);
+      return 1;
+    }
+  for (int g = 0; g < p.G; ++g)
+    if (!x[g]) { dta_set_error("dta_multistage_predict_ensemble: null input for network %d", g); return 1; }
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
+  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
+  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
+  if (rc) return rc;
+  SoftmaxMulti m;
+  memset(&m, 0, sizeof(m));
+  m.n = levels; m.B = p.B;
+  for (int l = 0; l < levels; ++l) {
+    SoftmaxLevel& a = m.lv[l];
+    for (int k = 0; k < lv[l].count; ++k) a.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
+    a.nsrc = lv[l].count; a.gate = gate ? gate + lv[l].first : nullptr; a.mean_out = lv[l].mean_scores; a.classes = lv[l].classes;
+    a.probs = probs ? probs[l] : nullptr; a.top_idx = top_idx[l]; a.top_score = top_score[l];
+  }
+  return launch_softmax_top2_ensemble(m, e, st);
+}
+
+int dta_hierarchy_resolve(int levels, const long long* const* top_idx, const float* const* top_score, int batch,
+                          const dta_hierarchy* table, long long* ens_label, float* ens_score, int* ens_level,
+                          const long long* labels, long long* confusion, void* stream) {
+  ResolveArgs a;
+  memset(&a, 0, sizeof(a));
+  if (!top_idx || !top_score || batch < 1) { dta_set_error("dta_hierarchy_resolve: null argument or empty batch"); return 1; }
+  if (hierarchy_args("dta_hierarchy_resolve", levels, table, ens_label, ens_score, ens_level, labels, confusion, &a.e)) return 1;
+  for (int l = 0; l < levels; ++l) {
+    if (!top_idx[l] || !top_score[l]) { dta_set_error("dta_hierarchy_resolve: level %d has no top-2 arrays", l); return 1; }
+    a.top_idx[l] = top_idx[l]; a.top_score[l] = top_score[l];
+  }
+  a.n = levels; a.B = batch;
+  return launch_hierarchy_resolve(a, (hipStream_t)stream);
+}
+
 int dta_multistage_backward(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                             void* workspace, const dta_subnet_grads* grads, const float* gate, void* stream) {
   Plan p; dta_net_desc dd;

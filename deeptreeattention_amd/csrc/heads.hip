@@ -816,6 +816,155 @@ __global__ __launch_bounds__(256) void k_softmax_top2_multi(SoftmaxMulti m) {
     if (a.top_score) { a.top_score[row * 2] = b1; a.top_score[row * 2 + 1] = b2; }
   }
 }
+// k_softmax_top2_multi's row, statement for statement (that kernel stays as it is: its code is the yardstick of
+// dta_multistage_predict), for the kernel below, whose waves need the row's top-1 afterwards: every lane returns with
+// the row's top-1 class and probability (i1, b1)
+__device__ __forceinline__ void softmax_top2_row(const SoftmaxLevel& a, int row, int lane, float& b1, int& i1) {
+  const int classes = a.classes;
+  float kept = 0.f;
+  unsigned use = 0u;
+#pragma unroll
+  for (int k = 0; k < MAXG; ++k)
+    if (k < a.nsrc && (!a.gate || a.gate[k] > 0.f)) { use |= 1u << k; kept += 1.f; }
+  const float kinv = 1.f / kept;                      // nothing kept: inf, 0 * inf = NaN -- an empty mean, as k_mean_scores
+  auto zat = [&](int n) __attribute__((always_inline)) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXG; ++k)
+      if ((use >> k) & 1u) acc += a.src[k][(size_t)row * classes + n];
+    return acc * kinv;
+  };
+  // the first 256 classes of the row live in registers (four per lane); wider rows re-form the rest
+  float zc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; zc[k] = n < classes ? zat(n) : -3.4e38f; }
+  // visit this lane's classes in ascending order: the register-held ones statically indexed, then the re-formed tail
+  auto each = [&](auto&& f) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; if (n < classes) f(n, zc[k]); }
+    for (int n = lane + 256; n < classes; n += 64) f(n, zat(n));
+  };
+  float mx = -3.4e38f;
+  each([&](int, float z) __attribute__((always_inline)) { mx = fmaxf(mx, z); });
+  mx = wave_max(mx);
+  float se = 0.f;
+  each([&](int, float z) __attribute__((always_inline)) { se += __expf(z - mx); });
+  se = wave_sum(se);
+  const float inv = 1.f / se;
+  float b2 = -1.f;
+  int i2 = -1;
+  b1 = -1.f; i1 = -1;
+#define DTA_ROW_OUT(n_, z_)                                                                      \
+  {                                                                                              \
+    const int nn = (n_);                                                                         \
+    const float zz = (z_);                                                                       \
+    if (a.mean_out) a.mean_out[(size_t)row * classes + nn] = zz;                                 \
+    const float pr = __expf(zz - mx) * inv;                                                      \
+    if (a.probs) a.probs[(size_t)row * classes + nn] = pr;                                       \
+    if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = nn; }                                         \
+    else if (pr > b2) { b2 = pr; i2 = nn; }                                                      \
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; if (n < classes) DTA_ROW_OUT(n, zc[k]) }
+  for (int n = lane + 256; n < classes; n += 64) DTA_ROW_OUT(n, zat(n))
+#undef DTA_ROW_OUT
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
+    int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
+    auto better = [](float a_, int ia, float b_, int ib) { return a_ > b_ || (a_ == b_ && ia >= 0 && (ib < 0 || ia < ib)); };
+    float n1, n2; int j1, j2;
+    if (better(b1, i1, ob1, oi1)) {
+      n1 = b1; j1 = i1;
+      if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
+    } else {
+      n1 = ob1; j1 = oi1;
+      if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
+    }
+    b1 = n1; i1 = j1; b2 = n2; i2 = j2;
+  }
+  if (lane == 0) {
+    if (a.top_idx) { a.top_idx[row * 2] = i1; a.top_idx[row * 2 + 1] = i2; }
+    if (a.top_score) { a.top_score[row * 2] = b1; a.top_score[row * 2 + 1] = b2; }
+  }
+}
+// ------------------------------------------------------------------------------------------------
+// The hierarchy walk (reference multi_stage.py:404-434, `MultiStage.ensemble`, as a table: hierarchy.py).  Eight adjacent
+// lanes serve one crop, lane k of them holding level k's top-1 class and probability: each looks its class up (one table
+// load per level, all in flight together), then the walk itself is at most `levels` register shuffles.  Nothing the table
+// or the class indices hold can take a load out of bounds: a class outside its level's range, or an edge that does not
+// lead to a later level, ends the walk there (label -1 for the former).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void hierarchy_walk(const HierarchyArgs& e, int levels, int row, bool row_ok, int lane, int cls, float score) {
+  const int lvl = lane & 7;
+  int lo = 0, hi = 0;
+#pragma unroll
+  for (int k = 0; k < BLEND_CE_MULTI_MAX; ++k)
+    if (lvl == k) { lo = e.off[k]; hi = e.off[k + 1]; }
+  int nx = -1, sp = -1;
+  if (row_ok && lvl < levels && cls >= 0 && cls < hi - lo) { nx = e.next[lo + cls]; sp = e.species[lo + cls]; }
+  int cur = 0;
+#pragma unroll
+  for (int s = 1; s < BLEND_CE_MULTI_MAX; ++s) {
+    const int nxt = __shfl(nx, cur, 8);
+    if (nxt > cur && nxt < levels) cur = nxt;
+  }
+  const int label = __shfl(sp, cur, 8);
+  const float sc = __shfl(score, cur, 8);
+  if (row_ok && lvl == 0) {
+    e.ens_label[row] = label; e.ens_score[row] = sc; e.ens_level[row] = cur;
+    if (e.labels) {
+      // rows = label, columns = prediction; 64-bit integer adds commute, so the matrix does not depend on arrival order
+      const long long y = e.labels[row];
+      if (y >= 0 && y < e.n_species && label >= 0 && label < e.n_species)
+        atomicAdd(reinterpret_cast<unsigned long long*>(e.confusion) + (size_t)y * e.n_species + label, 1ull);
+    }
+  }
+}
+// k_softmax_top2_multi with the levels of a crop as the WAVES of one workgroup (wave = level, workgroup = crop) instead of
+// workgroups of their own: the same waves doing the same arithmetic, and the levels' top-1 of a crop meet in LDS behind
+// one barrier, where the first eight lanes walk the table
+__global__ __launch_bounds__(64 * BLEND_CE_MULTI_MAX) void k_softmax_top2_ensemble(SoftmaxMulti m, HierarchyArgs e) {
+  __shared__ int s_cls[BLEND_CE_MULTI_MAX];
+  __shared__ float s_score[BLEND_CE_MULTI_MAX];
+  const int lane = threadIdx.x & 63, lvl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), row = blockIdx.x;
+  float b1; int i1;
+  softmax_top2_row(m.lv[lvl], row, lane, b1, i1);
+  if (lane == 0) { s_cls[lvl] = i1; s_score[lvl] = b1; }
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  const bool mine = lane < m.n;
+  hierarchy_walk(e, m.n, row, lane < 8, lane, mine ? s_cls[lane & 7] : -1, mine ? s_score[lane & 7] : 0.f);
+}
+// the walk alone, on per-level [B][2] top-2 arrays: eight crops per wave
+__global__ __launch_bounds__(256) void k_hierarchy_resolve(ResolveArgs a) {
+  const int lane = threadIdx.x & 63, lvl = lane & 7;
+  const int row = (blockIdx.x * 256 + threadIdx.x) >> 3;
+  const bool row_ok = row < a.B;
+  const long long* ti = nullptr; const float* ts = nullptr;
+#pragma unroll
+  for (int k = 0; k < BLEND_CE_MULTI_MAX; ++k)
+    if (lvl == k) { ti = a.top_idx[k]; ts = a.top_score[k]; }
+  int cls = -1; float score = 0.f;
+  if (row_ok && lvl < a.n) {
+    const long long c = ti[(size_t)row * 2];
+    cls = (c >= 0 && c < 0x7fffffff) ? (int)c : -1;
+    score = ts[(size_t)row * 2];
+  }
+  hierarchy_walk(a.e, a.n, row, row_ok, lane, cls, score);
+}
+int launch_softmax_top2_ensemble(const SoftmaxMulti& m, const HierarchyArgs& e, hipStream_t st) {
+  if (m.n < 1 || m.n > BLEND_CE_MULTI_MAX) { dta_set_error("softmax_top2_ensemble: 1..%d levels", BLEND_CE_MULTI_MAX); return 1; }
+  hipLaunchKernelGGL(k_softmax_top2_ensemble, dim3(m.B), dim3(64 * m.n), 0, st, m, e);
+  DTA_CHECK_LAUNCH("k_softmax_top2_ensemble");
+  return 0;
+}
+int launch_hierarchy_resolve(const ResolveArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > BLEND_CE_MULTI_MAX) { dta_set_error("hierarchy_resolve: 1..%d levels", BLEND_CE_MULTI_MAX); return 1; }
+  hipLaunchKernelGGL(k_hierarchy_resolve, dim3((a.B + 31) / 32), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_hierarchy_resolve");
+  return 0;
+}
 int launch_softmax_top2_multi(const SoftmaxMulti& m, hipStream_t st) {
   if (m.n < 1 || m.n > BLEND_CE_MULTI_MAX) { dta_set_error("softmax_top2_multi: 1..%d levels", BLEND_CE_MULTI_MAX); return 1; }
   hipLaunchKernelGGL(k_softmax_top2_multi, dim3((m.B + 3) / 4, m.n), dim3(256), 0, st, m);

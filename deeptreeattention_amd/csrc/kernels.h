@@ -649,5 +649,16 @@ struct SoftmaxLevel { const float* src[MAXG]; int nsrc; const float* gate; float
                       float* probs; long long* top_idx; float* top_score; };
 struct SoftmaxMulti { SoftmaxLevel lv[BLEND_CE_MULTI_MAX]; int n, B; };
 int launch_softmax_top2_multi(const SoftmaxMulti& m, hipStream_t st);
+// ... and behind it, in the same launch, the walk down the hierarchy that turns the levels' top-1 classes into ONE species
+// label per crop (reference multi_stage.py:404-434; the table is hierarchy.py's): next / species hold every level's classes
+// back to back, level l's at off[l] .. off[l + 1].  ens_score is the top-1 probability of the level the walk ended on,
+// ens_level that level.  labels / confusion (both or neither): confusion[label][ens_label] += 1 (64-bit integer atomics).
+struct HierarchyArgs { const int* next; const int* species; int off[BLEND_CE_MULTI_MAX + 1]; int n_species;
+                       long long* ens_label; float* ens_score; int* ens_level;
+                       const long long* labels; long long* confusion; };
+int launch_softmax_top2_ensemble(const SoftmaxMulti& m, const HierarchyArgs& e, hipStream_t st);
+// the walk alone, on per-level [B][2] top-2 arrays (the first column is read)
+struct ResolveArgs { const long long* top_idx[BLEND_CE_MULTI_MAX]; const float* top_score[BLEND_CE_MULTI_MAX]; int n, B; HierarchyArgs e; };
+int launch_hierarchy_resolve(const ResolveArgs& a, hipStream_t st);
 
 }  // namespace dta

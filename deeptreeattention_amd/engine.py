@@ -1174,9 +1174,11 @@ class MultiStageTrainer:
     weight vector, one Adam and one learning rate per level, selected by Lightning's optimizer_idx /
     dataloader_idx.  Batches keep the reference's structure: (individual, {"HSI": [year tensors]}, labels)."""
 
-    def __init__(self, models, lrs, loss_weights=None, **kwargs):
+    def __init__(self, models, lrs, loss_weights=None, hierarchy=None, **kwargs):
         loss_weights = loss_weights or [None] * len(models)
         self.levels = [EnsembleTrainer(m, lr, w, **kwargs) for m, lr, w in zip(models, lrs, loss_weights)]
+        self.hierarchy = hierarchy       # hierarchy.Hierarchy over the levels (predict_ensemble)
+        self.confusion = None            # predict_ensemble(labels=...) counts here: int64 [n_species][n_species], rows = label
         self._ws = None
         self._ws_key = None
         self._gate_banks = None
@@ -1337,6 +1339,35 @@ class MultiStageTrainer:
             # every level sees the same crops: all levels x years networks in ONE eval-mode launch chain
             return individual, [o[0].clone() for o in self._ms_predictor(images, True, present)]
         return individual, [pr(images, True, present)[0].clone() for pr in self._predictors]
+
+    def predict_ensemble(self, batch, batch_idx=0, present=None, labels=None):
+        """multi_stage.py:306-318 followed by :368-434 (`gather_predictions` + `ensemble`) on the device: ONE species label,
+        its score and the level that decided per crop.  Returns (individual, ens_label, ens_score, ens_level).  One launch
+        chain with the walk in its last launch when the levels x years networks fit one (MultiStagePredictor.ensemble), else
+        a cached Predictor per level followed by the walk alone (dta_hierarchy_resolve).  labels (species labels, int64 [B]):
+        the call also counts into self.confusion."""
+        if self.hierarchy is None:
+            raise RuntimeError("predict_ensemble needs a hierarchy (MultiStageTrainer(..., hierarchy=...))")
+        individual, inputs = batch[0], batch[1]
+        if not hasattr(self, "_predictors"):
+            self._predictors = [Predictor(t.model) for t in self.levels]
+            self._ms_predictor = MultiStagePredictor([t.model for t in self.levels])
+        images = inputs["HSI"]
+        if labels is not None:
+            labels = _species_labels(labels, self._ms_predictor.device)
+            if self.confusion is None:
+                n = self.hierarchy.n_species
+                self.confusion = torch.zeros(n, n, dtype=torch.int64, device=self._ms_predictor.device)
+        if self._ms_predictor.supported(len(images)):
+            self._ms_predictor.hierarchy = self.hierarchy
+            self._ms_predictor.confusion = self.confusion
+            ens = self._ms_predictor.ensemble(images, present, labels)
+        else:
+            outs = [pr(images, False, present) for pr in self._predictors]
+            self._ens = resolve_hierarchy(self.hierarchy, [o[1] for o in outs], [o[2] for o in outs], labels,
+                                          self.confusion if labels is not None else None, getattr(self, "_ens", None))
+            ens = self._ens
+        return (individual,) + tuple(t.clone() for t in ens)
 
 
 class MetadataTrainer:
@@ -1810,7 +1841,7 @@ class MultiStagePredictor:
     models: the levels' learned_ensembles (same year count, bands and precision).  Missing years are decided on the device
     unless `present` (one list of booleans, shared by the levels: they see the same crops) is passed."""
 
-    def __init__(self, models, frozen=False):
+    def __init__(self, models, frozen=False, hierarchy=None):
         self.frozen = bool(frozen)      # as Predictor: keep the weight re-layouts of the first call (refresh() after updates)
         self._packed = False
         self.preds = [Predictor(m) for m in models]
@@ -1818,6 +1849,10 @@ class MultiStagePredictor:
             raise TypeError("MultiStagePredictor needs year.learned_ensemble levels")
         self.device = self.preds[0].device
         self._key = None
+        # hierarchy.Hierarchy over these levels: ensemble() then also walks it (ONE species label per crop) in the epilogue launch
+        self.hierarchy = hierarchy
+        self.confusion = None           # int64 [n_species][n_species], rows = label: created by the first ensemble(labels=...)
+        self._ens = None
 
     def refresh(self):
         """After in-place weight updates of a frozen predictor (or replaced parameter tensors): rebuild everything."""
@@ -1872,6 +1907,31 @@ class MultiStagePredictor:
 
     def __call__(self, images, return_probs=True, present=None):
         """Returns one (probs or None, top_idx [B,2], top_score [B,2]) triple per level; buffers are reused across calls."""
+        return self._run(images, return_probs, present, None)
+
+    def ensemble(self, images, present=None, labels=None, return_probs=True):
+        """The same chain with the hierarchy walk in its last launch (reference multi_stage.py:368-434, `gather_predictions`
+        + `ensemble`): returns (ens_label int64 [B], ens_score float32 [B], ens_level int32 [B]) -- the species, the top-1
+        probability of the level that decided, and that level; buffers are reused across calls.  labels (int64 [B], species
+        labels): the call also counts into `self.confusion` (rows = label, columns = prediction; zero it to start a new
+        epoch).  The call's per-level outputs are in self.probs / self.top_idx / self.top_score as after __call__
+        (`per_level()` hands them back as __call__'s triples)."""
+        if self.hierarchy is None:
+            raise RuntimeError("MultiStagePredictor.ensemble needs a hierarchy (MultiStagePredictor(models, hierarchy=...))")
+        if self.hierarchy.levels != len(self.preds):
+            raise ValueError("the hierarchy has {} levels, the predictor {}".format(self.hierarchy.levels, len(self.preds)))
+        if labels is not None:
+            labels = _species_labels(labels, self.device)
+            if self.confusion is None:
+                self.confusion = torch.zeros(self.hierarchy.n_species, self.hierarchy.n_species, dtype=torch.int64, device=self.device)
+        self._run(images, return_probs, present, (labels,))
+        return self._ens
+
+    def per_level(self, return_probs=True):
+        """The last call's (probs or None, top_idx, top_score) triple per level."""
+        return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(len(self.preds))]
+
+    def _run(self, images, return_probs, present, ens):
         L = _lib.lib()
         st = _lib.current_stream_ptr()
         nl = len(self.preds)
@@ -1896,11 +1956,71 @@ class MultiStagePredictor:
             gate = flags.repeat(nl)                 # the (level, year) groups' flags: the years' flags once per level
         # forward of all levels x years + ONE launch for every level's mean over its years, softmax and top-2
         desc = self.desc_reuse if (self.frozen and self._packed) else self.desc
-        _lib.check(L.dta_multistage_predict(C.byref(desc), nl, self.lv, self.nets, xptr, _lib.ptr(gate), _lib.ptr(self.ws),
-                                            self._pp if return_probs else None, self._pi, self._ps, st), "dta_multistage_predict")
+        if ens is None:
+            _lib.check(L.dta_multistage_predict(C.byref(desc), nl, self.lv, self.nets, xptr, _lib.ptr(gate), _lib.ptr(self.ws),
+                                                self._pp if return_probs else None, self._pi, self._ps, st), "dta_multistage_predict")
+        else:
+            # ... and the walk down the hierarchy (and the confusion count) in that same launch
+            labels, = ens
+            B = xs[0].shape[0]
+            if labels is not None and labels.shape[0] != B:
+                raise ValueError("one species label per crop")
+            if self._ens is None or self._ens[0].shape[0] != B:
+                self._ens = _ensemble_buffers(B, self.device)
+            table = self.hierarchy.c_table(self.device)
+            _lib.check(L.dta_multistage_predict_ensemble(C.byref(desc), nl, self.lv, self.nets, xptr, _lib.ptr(gate), _lib.ptr(self.ws),
+                                                         self._pp if return_probs else None, self._pi, self._ps, C.byref(table),
+                                                         _lib.ptr(self._ens[0]), _lib.ptr(self._ens[1]), _lib.ptr(self._ens[2]),
+                                                         _lib.ptr(labels), _lib.ptr(self.confusion if labels is not None else None), st),
+                       "dta_multistage_predict_ensemble")
+            xs = (xs, labels)
         self._packed = True
         self._live = (xs, gate)
         return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(nl)]
+
+
+def _ensemble_buffers(B, device):
+    return (torch.empty(B, dtype=torch.int64, device=device), torch.empty(B, dtype=torch.float32, device=device),
+            torch.empty(B, dtype=torch.int32, device=device))
+
+
+def _species_labels(labels, device):
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 1:
+        raise ValueError("species labels are one integer per crop")
+    return labels.to(device=device, dtype=torch.int64).contiguous()
+
+
+def resolve_hierarchy(hierarchy, top_idx, top_score, labels=None, confusion=None, out=None):
+    """The hierarchy walk alone (dta_hierarchy_resolve), for levels that were predicted one by one: top_idx / top_score are
+    the levels' [B, 2] top-2 tensors on the device (as Predictor / predict() return them).  Returns (ens_label, ens_score,
+    ens_level) as MultiStagePredictor.ensemble does; `out` reuses such a triple.  labels + confusion (int64 [n_species,
+    n_species] on the device): confusion[label][ens_label] += 1."""
+    L = _lib.lib()
+    nl = len(top_idx)
+    if nl != hierarchy.levels or len(top_score) != nl:
+        raise ValueError("the hierarchy has {} levels: one top_idx and one top_score tensor per level".format(hierarchy.levels))
+    device = top_idx[0].device
+    B = top_idx[0].shape[0]
+    for l, (i, s_) in enumerate(zip(top_idx, top_score)):
+        if (i.dtype != torch.int64 or s_.dtype != torch.float32 or tuple(i.shape) != (B, 2) or tuple(s_.shape) != (B, 2)
+                or not i.is_contiguous() or not s_.is_contiguous() or i.device != device or s_.device != device):
+            raise ValueError("level {}: top_idx int64 [B, 2] and top_score float32 [B, 2], contiguous, on one device".format(l))
+    if (labels is None) != (confusion is None):
+        raise ValueError("labels and confusion come together or not at all")
+    if labels is not None:
+        labels = _species_labels(labels, device)
+        n = hierarchy.n_species
+        if labels.shape[0] != B or confusion.dtype != torch.int64 or tuple(confusion.shape) != (n, n) or not confusion.is_contiguous():
+            raise ValueError("one label per crop and an int64 [{0}, {0}] confusion matrix".format(n))
+    if out is None or out[0].shape[0] != B:
+        out = _ensemble_buffers(B, device)
+    table = hierarchy.c_table(device)
+    pi = (C.c_void_p * nl)(*[t.data_ptr() for t in top_idx])
+    ps = (C.c_void_p * nl)(*[t.data_ptr() for t in top_score])
+    _lib.check(L.dta_hierarchy_resolve(nl, pi, ps, B, C.byref(table), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
+                                       _lib.ptr(labels), _lib.ptr(confusion), _lib.current_stream_ptr()), "dta_hierarchy_resolve")
+    return out
 
 
 _PREDICTORS = None      # model -> Predictor, weakly keyed: nothing is stored on the module (deepcopy / torch.save stay clean)

@@ -12,6 +12,8 @@ Lightning itself is out of scope; what a user of the hot path need
   * `fit`                   - epochs of `training_step` / `validation_step` + the scheduler, as Trainer.fit runs them;
   * `fit_multistage`        - the same for the reference's MultiStage module (train.py:75-100): every level of a batch in one
                               launch chain, per-level validation loaders and plateau schedulers.
+  * `predict_multistage`    - the prediction loop of src/predict.py:140-151 for a MultiStage module, ending in ONE species label
+                              per crop (multi_stage.py:368-434) and, with labels, the confusion matrix of the run.
 No arithmetic happens here; every step is the HIP path behind `engine.FusedTrainer` and friends.
 """
 import torch
@@ -195,3 +197,36 @@ def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128,
         if log:
             log(rec)
     return history
+
+
+def predict_multistage(trainer, data, batch_size=64, labels=False):
+    """The `predict_species` loop of the reference (src/predict.py:140-151: `trainer.predict(m, dataloaders=...)`, then
+    `gather_predictions` and `ensemble`, multi_stage.py:368-434) for an engine.MultiStageTrainer with a hierarchy: batches
+    of `data` (a SyntheticTreeDataset(years=...) or anything with `.loader(batch_size)`) through `predict_ensemble`, results
+    kept on the device, ONE device-to-host copy at the end.  labels=True: the batches' labels are species labels, and the
+    run's confusion matrix (rows = label, columns = prediction; `hierarchy.scores_from_confusion` turns it into
+    evaluation_scores' figures) is counted on the device along the way.
+    Returns a dict of NumPy arrays: individual, ens_label (int64), ens_score (float32), ens_level (int32) -- one row per
+    crop, in the loader's order -- and confusion (int64) when labels are given."""
+    import numpy as np
+    if labels:
+        had = trainer.confusion
+        trainer.confusion = None         # this run's own count
+    names, parts = [], []
+    try:
+        for i, batch in enumerate(data.loader(batch_size)):
+            out = trainer.predict_ensemble(batch, i, None, batch[2] if labels else None)
+            names += list(out[0])
+            parts.append(out[1:])
+        conf = trainer.confusion if labels else None
+    finally:
+        if labels:
+            trainer.confusion = had
+    if not parts:
+        raise ValueError("predict_multistage: the dataset yields no batch")
+    lab, sc, lev = (torch.cat([p[k] for p in parts]) for k in range(3))
+    res = {"individual": np.array(names), "ens_label": lab.cpu().numpy(), "ens_score": sc.cpu().numpy(),
+           "ens_level": lev.cpu().numpy()}
+    if labels:
+        res["confusion"] = conf.cpu().numpy()
+    return res

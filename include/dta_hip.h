@@ -362,6 +362,38 @@ int dta_multistage_predict(const dta_net_desc* d, int levels, const dta_level* l
 int dta_multistage_backward(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                             void* workspace, const dta_subnet_grads* grads, const float* gate, void* stream);
 
+/* ---- Hierarchical ensemble label (reference multi_stage.py:368-402 gather_predictions + :404-434 ensemble: the levels'
+ * top-1 classes of a crop become ONE species label and score by a walk down the hierarchy; :436-485 evaluation_scores:
+ * per-species accuracy / precision from the labels).  The hierarchy is a table: for level l and class c,
+ * next[off[l] + c] is the level to consult next (always a later one) or -1, and species[off[l] + c] the species label of
+ * a terminal class.  The walk starts at level 0.
+ *  table (device int32): off[levels + 1], next[off[levels]], species[off[levels]]
+ *  classes: every level's class count on the host (off[l + 1] - off[l]); the calls check it against their level arguments
+ * Outputs per crop: ens_label int64 [batch] (-1 where a level's top-1 class is outside its range, e.g. a row of NaN),
+ * ens_score float32 [batch] (the top-1 probability of the level the walk ended on: that level's top_score[:, 0], bit for
+ * bit), ens_level int32 [batch] (that level).
+ * labels (device int64 [batch], species labels) and confusion (device int64 [n_species][n_species], rows = label,
+ * columns = prediction) come together or not at all: confusion is ACCUMULATED into with 64-bit integer atomic adds
+ * (order-independent), so a caller sums over an epoch without a launch of its own; a label or prediction outside
+ * [0, n_species) is skipped. */
+typedef struct dta_hierarchy {
+  int levels, n_species;
+  int classes[DTA_MAX_LEVELS];
+  const int* table;
+} dta_hierarchy;
+/* dta_multistage_predict with the walk in the SAME launch as the levels' softmax + top-2 (still one launch behind the
+ * forward); the per-level outputs are dta_multistage_predict's, bit for bit. */
+int dta_multistage_predict_ensemble(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
+                                    const float* const* x, const float* gate, void* workspace, float* const* probs,
+                                    long long* const* top_idx, float* const* top_score, const dta_hierarchy* table,
+                                    long long* ens_label, float* ens_score, int* ens_level, const long long* labels,
+                                    long long* confusion, void* stream);
+/* The walk alone, on per-level [batch][2] top-2 arrays as dta_softmax_top2 / dta_multistage_predict leave them (HOST arrays
+ * of `levels` device pointers; the first column is read): for levels that were predicted one by one. */
+int dta_hierarchy_resolve(int levels, const long long* const* top_idx, const float* const* top_score, int batch,
+                          const dta_hierarchy* table, long long* ens_label, float* ens_score, int* ens_level,
+                          const long long* labels, long long* confusion, void* stream);
+
 /* ---- Peer gradient exchange: data-parallel training with one process per GPU of ONE node (reference train.py:89-98:
  * Lightning DDP all-reduces every parameter's gradient between loss.backward() and optimizer.step()).  Here the sum over
  * ranks and the Adam step are ONE launch on the caller's compute stream: every rank pulls its shard of all ranks'
