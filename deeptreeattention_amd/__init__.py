@@ -5,10 +5,14 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.year       <->  src/models/year.py        (learned_ensemble)
     deeptreeattention_amd.engine     fused train step (forward + weighted CE + backward + Adam, optional RCCL DDP)
     deeptreeattention_amd.hierarchy  <->  src/models/multi_stage.py:368-485 (the levels' predictions -> one species label)
+    deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
+                                     metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.
 """
 from . import Hang2020  # noqa: F401
 from .Hang2020 import set_default_precision, get_default_precision  # noqa: F401
 from .hierarchy import Hierarchy, scores_from_confusion  # noqa: F401
+from .loop import validate, validate_multistage  # noqa: F401
 
-__all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion"]
+__all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
+           "validate", "validate_multistage"]

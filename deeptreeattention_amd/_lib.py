@@ -78,6 +78,12 @@ class Level(C.Structure):           # dta_level
 
 
 MAX_LEVELS = 8   # DTA_MAX_LEVELS
+EVAL_TOP_K_MAX = 8   # DTA_EVAL_TOP_K_MAX
+
+
+class EvalLevel(C.Structure):       # dta_eval_level
+    _fields_ = [("probs", C.c_void_p), ("top_idx", C.c_void_p), ("top_score", C.c_void_p), ("confusion", C.c_void_p),
+                ("counts", C.c_void_p), ("loss_acc", C.c_void_p), ("top_k", C.c_int)]
 
 
 class HierarchyTable(C.Structure):  # dta_hierarchy
@@ -194,6 +200,12 @@ def lib():
         L.dta_hierarchy_resolve.restype = C.c_int
         L.dta_hierarchy_resolve.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(HierarchyTable),
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dta_multistage_validate.restype = C.c_int
+        L.dta_multistage_validate.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(EvalLevel),
+                                              C.POINTER(SubnetParams), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dta_eval_metrics.restype = C.c_int
+        L.dta_eval_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(EvalLevel), C.c_void_p]
         L.dta_multistage_backward.restype = C.c_int
         L.dta_multistage_backward.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams), C.c_void_p,
                                               C.POINTER(SubnetGrads), C.c_void_p, C.c_void_p]

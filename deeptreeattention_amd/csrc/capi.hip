@@ -1267,6 +1267,68 @@ int dta_multistage_predict(const dta_net_desc* d, int levels, const dta_level* l
   return launch_softmax_top2_multi(m, st);
 }
 
+// ---- validation: eval-mode forward of every level + ONE epilogue launch (loss, softmax, top-2, metric counts) ----
+static int eval_level_args(const char* who, int l, const dta_eval_level* ev, EvalLevel* e) {
+  if (ev->top_k < 1 || ev->top_k > DTA_EVAL_TOP_K_MAX) { dta_set_error("%s: level %d: top_k must be 1..%d, got %d", who, l, DTA_EVAL_TOP_K_MAX, ev->top_k); return 1; }
+  static_assert(DTA_EVAL_TOP_K_MAX == EVAL_TOP_K_MAX, "header and kernel disagree");
+  if (!ev->top_idx || !ev->top_score) { dta_set_error("%s: level %d: top_idx and top_score are required", who, l); return 1; }
+  e->probs = ev->probs; e->top_idx = ev->top_idx; e->top_score = ev->top_score;
+  e->confusion = ev->confusion; e->counts = ev->counts; e->loss_acc = ev->loss_acc; e->top_k = ev->top_k;
+  return 0;
+}
+
+int dta_multistage_validate(const dta_net_desc* d, int levels, const dta_level* lv, const dta_eval_level* ev,
+                            const dta_subnet_params* nets, const float* const* x, const float* gate,
+                            void* workspace, void* stream) {
+  Plan p; dta_net_desc dd;
+  const char* who = "dta_multistage_validate";
+  if (!d || !lv || !ev) { dta_set_error("%s: null argument", who); return 1; }
+  if (d->training != 0) { dta_set_error("%s: validation runs eval-mode BatchNorm: the descriptor's training must be 0", who); return 1; }
+  if (!(d->heads_mask & DTA_FORWARD_ONLY)) { dta_set_error("%s: the descriptor's heads_mask must carry DTA_FORWARD_ONLY", who); return 1; }
+  if (d->heads_mask & DTA_REUSE_PACKED) { dta_set_error("%s: DTA_REUSE_PACKED is refused: validation follows weight updates", who); return 1; }
+  if (multistage_desc(d, levels, lv, &dd, &p, who)) return 1;
+  EvalMulti m;
+  memset(&m, 0, sizeof(m));
+  m.n = levels;
+  for (int l = 0; l < levels; ++l)
+    if (eval_level_args(who, l, ev + l, &m.lv[l])) return 1;
+  if (!nets || !x || !workspace) { dta_set_error("%s: null argument", who); return 1; }
+  for (int g = 0; g < p.G; ++g)
+    if (!x[g]) { dta_set_error("%s: null input for network %d", who, g); return 1; }
+  for (int l = 0; l < levels; ++l)
+    if (!lv[l].labels || !lv[l].loss || !lv[l].scratch) { dta_set_error("%s: level %d: labels, loss and scratch are required", who, l); return 1; }
+  if (dd.dtype != DTA_BF16 && dd.dtype != DTA_F32) { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
+  else rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
+  if (rc) return rc;
+  for (int l = 0; l < levels; ++l) {
+    BlendCeArgs& a = m.lv[l].ce;
+    a.gscale = 1.f;
+    for (int k = 0; k < lv[l].count; ++k) a.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
+    a.nsrc = lv[l].count; a.src_gate = gate ? gate + lv[l].first : nullptr; a.kept_out = lv[l].kept; a.joint = lv[l].mean_scores;
+    a.labels = lv[l].labels; a.weight = lv[l].weight; a.loss = lv[l].loss; a.rowtmp = lv[l].scratch;
+    a.B = p.B; a.classes = lv[l].classes;
+  }
+  return launch_eval_metrics_multi(m, st);
+}
+
+int dta_eval_metrics(const float* scores, const long long* labels, const float* weight, int batch, int classes,
+                     float* loss, float* scratch, const dta_eval_level* ev, void* stream) {
+  const char* who = "dta_eval_metrics";
+  if (!scores || !labels || !loss || !scratch || !ev) { dta_set_error("%s: null argument", who); return 1; }
+  if (batch < 1 || classes < 1) { dta_set_error("%s: batch and classes must be positive, got %d and %d", who, batch, classes); return 1; }
+  EvalMulti m;
+  memset(&m, 0, sizeof(m));
+  m.n = 1;
+  if (eval_level_args(who, 0, ev, &m.lv[0])) return 1;
+  BlendCeArgs& a = m.lv[0].ce;
+  a.gscale = 1.f;
+  a.spec = scores; a.labels = labels; a.weight = weight; a.loss = loss; a.rowtmp = scratch; a.B = batch; a.classes = classes;
+  return launch_eval_metrics_multi(m, (hipStream_t)stream);
+}
+
 // the hierarchy arguments of the two ensemble-label calls, checked on the host before anything is launched
 static int hierarchy_args(const char* who, int levels, const dta_hierarchy* h, long long* ens_label, float* ens_score, int* ens_level,
                           const long long* labels, long long* confusion, HierarchyArgs* e) {

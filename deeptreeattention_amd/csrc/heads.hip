@@ -979,6 +979,144 @@ int launch_softmax_top2(const float* logits, int B, int classes, float* probs, l
 }
 
 // ------------------------------------------------------------------------------------------------
+// Validation epilogue (reference multi_stage.py:290-304 validation_step: weighted cross-entropy + softmax + the metric
+// collection of :20-28 / main.py:53-61; :323-366 validation_epoch_end's per-level figures): per row the softmax, the top-2
+// and the rank of the label among the probabilities (k_softmax_top2_multi's arithmetic, ties towards the lower index), the
+// loss through blend_ce_body (forward part: no dlogits), and the epoch accumulators the call ADDS to.
+//  confusion / counts: 64-bit integer atomics (they commute); loss_acc: one writer per launch and level -- thread 0 of the
+//  workgroup that finished the batch loss -- with plain double arithmetic, so reruns are bit-identical.
+// A row whose label is outside [0, classes) or whose scores are NaN (top-1 = -1) is left out of the counts.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void eval_row(const EvalLevel& e, int row, int lane, int* s_cnt) {
+  const BlendCeArgs& a = e.ce;
+  const int classes = a.classes;
+  float kept = 0.f;
+  unsigned use = 0u;
+#pragma unroll
+  for (int k = 0; k < MAXG; ++k)
+    if (k < a.nsrc && (!a.src_gate || a.src_gate[k] > 0.f)) { use |= 1u << k; kept += 1.f; }
+  const float kinv = 1.f / kept;                      // nothing kept: inf, 0 * inf = NaN -- an empty mean, as k_mean_scores
+  const bool direct = a.nsrc == 0;                    // single-model use: the scores are one [B][classes] array
+  auto zat = [&](int n) __attribute__((always_inline)) {
+    if (direct) return a.spec[(size_t)row * classes + n];
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXG; ++k)
+      if ((use >> k) & 1u) acc += a.src[k][(size_t)row * classes + n];
+    return acc * kinv;
+  };
+  // the first 256 classes of the row live in registers (four per lane, as named scalars: blend_ce_body below brings small
+  // arrays of its own, and one more here is what the compiler no longer keeps in registers); wider rows re-form the rest
+  const float z0 = lane < classes ? zat(lane) : -3.4e38f, z1 = lane + 64 < classes ? zat(lane + 64) : -3.4e38f;
+  const float z2 = lane + 128 < classes ? zat(lane + 128) : -3.4e38f, z3 = lane + 192 < classes ? zat(lane + 192) : -3.4e38f;
+  auto each = [&](auto&& f) __attribute__((always_inline)) {      // this lane's classes in ascending order
+    if (lane < classes) f(lane, z0);
+    if (lane + 64 < classes) f(lane + 64, z1);
+    if (lane + 128 < classes) f(lane + 128, z2);
+    if (lane + 192 < classes) f(lane + 192, z3);
+    for (int n = lane + 256; n < classes; n += 64) f(n, zat(n));
+  };
+  float mx = -3.4e38f;
+  each([&](int, float z) __attribute__((always_inline)) { mx = fmaxf(mx, z); });
+  mx = wave_max(mx);
+  float se = 0.f;
+  each([&](int, float z) __attribute__((always_inline)) { se += __expf(z - mx); });
+  se = wave_sum(se);
+  const float inv = 1.f / se;
+  float b1 = -1.f, b2 = -1.f;
+  int i1 = -1, i2 = -1;
+  // (a macro, as in k_softmax_top2_multi: through a lambda's by-reference captures the compare-and-replace below turns into
+  //  stores through a selected pointer, and b1 / b2 / i1 / i2 would live in the private segment)
+#define DTA_EVAL_ROW_OUT(n_, z_)                                                                 \
+  {                                                                                              \
+    const int nn = (n_);                                                                         \
+    const float pr = __expf((z_) - mx) * inv;                                                    \
+    if (e.probs) e.probs[(size_t)row * classes + nn] = pr;                                       \
+    if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = nn; }                                         \
+    else if (pr > b2) { b2 = pr; i2 = nn; }                                                      \
+  }
+  if (lane < classes) DTA_EVAL_ROW_OUT(lane, z0)
+  if (lane + 64 < classes) DTA_EVAL_ROW_OUT(lane + 64, z1)
+  if (lane + 128 < classes) DTA_EVAL_ROW_OUT(lane + 128, z2)
+  if (lane + 192 < classes) DTA_EVAL_ROW_OUT(lane + 192, z3)
+  for (int n = lane + 256; n < classes; n += 64) DTA_EVAL_ROW_OUT(n, zat(n))
+#undef DTA_EVAL_ROW_OUT
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
+    int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
+    auto better = [](float a_, int ia, float b_, int ib) { return a_ > b_ || (a_ == b_ && ia >= 0 && (ib < 0 || ia < ib)); };
+    float n1, n2; int j1, j2;
+    if (better(b1, i1, ob1, oi1)) {
+      n1 = b1; j1 = i1;
+      if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
+    } else {
+      n1 = ob1; j1 = oi1;
+      if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
+    }
+    b1 = n1; i1 = j1; b2 = n2; i2 = j2;
+  }
+  if (lane == 0) {
+    if (e.top_idx) { e.top_idx[row * 2] = i1; e.top_idx[row * 2 + 1] = i2; }
+    if (e.top_score) { e.top_score[row * 2] = b1; e.top_score[row * 2 + 1] = b2; }
+  }
+  const long long y = a.labels[row];
+  const bool ok = y >= 0 && y < classes && i1 >= 0;
+  if (!ok) return;                                    // (wave-uniform: y and the merged top-1 are the same on every lane)
+  // the label's rank: how many classes beat its probability (a tie goes to the lower index) -- the same __expf(z - mx) * inv
+  // on the same operands as above, so the label is rank 0 exactly when it is top_idx[0]
+  const float py = __expf(zat((int)y) - mx) * inv;
+  int rank = 0;
+  each([&](int n, float z) __attribute__((always_inline)) {
+    const float pr = __expf(z - mx) * inv;
+    if (pr > py || (pr == py && n < (int)y)) rank += 1;
+  });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o);
+  if (lane == 0) {
+    if (e.confusion) atomicAdd(reinterpret_cast<unsigned long long*>(e.confusion) + (size_t)y * classes + i1, 1ull);
+    atomicAdd(&s_cnt[0], 1);
+    if (i1 == (int)y) atomicAdd(&s_cnt[1], 1);
+    if (rank < e.top_k) atomicAdd(&s_cnt[2], 1);
+  }
+}
+__global__ __launch_bounds__(256) void k_eval_metrics_multi(EvalMulti m) {
+  __shared__ float sc[8];
+  __shared__ double sd[256];
+  __shared__ int is_last;
+  __shared__ int s_cnt[3];
+  const EvalLevel& e = m.lv[blockIdx.y];
+  const int t = threadIdx.x, row = blockIdx.x * 4 + (t >> 6);
+  if (t < 3) s_cnt[t] = 0;
+  __syncthreads();
+  if (row < e.ce.B) eval_row(e, row, t & 63, s_cnt);
+  blend_ce_body(e.ce, sc, sd, &is_last);             // (its barriers also close this workgroup's LDS counts)
+  if (t != 0) return;
+  if (e.counts) {
+    unsigned long long* c = reinterpret_cast<unsigned long long*>(e.counts);
+    if (s_cnt[0]) atomicAdd(c + 0, (unsigned long long)s_cnt[0]);
+    if (s_cnt[1]) atomicAdd(c + 1, (unsigned long long)s_cnt[1]);
+    if (s_cnt[2]) atomicAdd(c + 2, (unsigned long long)s_cnt[2]);
+    if (is_last) atomicAdd(c + 3, 1ull);
+  }
+  if (is_last && e.loss_acc) {
+    // the batch loss this thread has just written, weighted by the batch size as Lightning weights a logged batch value
+    e.loss_acc[0] += (double)e.ce.loss[0] * (double)e.ce.B;
+    e.loss_acc[1] += (double)e.ce.B;
+  }
+}
+int launch_eval_metrics_multi(const EvalMulti& m, hipStream_t st) {
+  if (m.n < 1 || m.n > BLEND_CE_MULTI_MAX) { dta_set_error("eval_metrics_multi: 1..%d levels", BLEND_CE_MULTI_MAX); return 1; }
+  for (int i = 0; i < m.n; ++i) {
+    if (m.lv[i].ce.B != m.lv[0].ce.B || m.lv[i].ce.B < 1) { dta_set_error("eval_metrics_multi: every level of the launch needs the same batch size"); return 1; }
+    if (m.lv[i].top_k < 1 || m.lv[i].top_k > EVAL_TOP_K_MAX) { dta_set_error("eval_metrics_multi: top_k must be 1..%d", EVAL_TOP_K_MAX); return 1; }
+  }
+  hipLaunchKernelGGL(k_eval_metrics_multi, dim3((m.lv[0].ce.B + 3) / 4, m.n), dim3(256), 0, st, m);
+  DTA_CHECK_LAUNCH("k_eval_metrics_multi");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // torch.optim.Adam (defaults: no weight decay, no amsgrad) over one flat fp32 buffer + the fp64 alpha.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void adam_block(const AdamArgs& a) {

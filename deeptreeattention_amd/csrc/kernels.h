@@ -660,5 +660,20 @@ int launch_softmax_top2_ensemble(const SoftmaxMulti& m, const HierarchyArgs& e, 
 // the walk alone, on per-level [B][2] top-2 arrays (the first column is read)
 struct ResolveArgs { const long long* top_idx[BLEND_CE_MULTI_MAX]; const float* top_score[BLEND_CE_MULTI_MAX]; int n, B; HierarchyArgs e; };
 int launch_hierarchy_resolve(const ResolveArgs& a, hipStream_t st);
+// Validation epilogue, up to 8 levels in ONE launch (blockIdx.y = level; every level the same batch size): what
+// k_blend_ce_multi (forward part: ce.dlogits stays NULL) and k_softmax_top2_multi do, plus the metric counts of a validation
+// epoch (reference multi_stage.py:290-304, :20-28, :323-366).  ce describes the scores (nsrc > 0: the mean over the kept
+// sources; nsrc == 0: ce.spec is one [B][classes] array, ce.spat NULL), labels, class weights, loss scalar and rowtmp
+// (B + 2 floats, last word zero on entry and left zero); ce.joint (may be NULL) receives the scores.
+//  probs (may be NULL) / top_idx / top_score (may be NULL): as SoftmaxLevel's
+//  confusion (may be NULL): int64 [classes][classes], confusion[label][top-1] += 1
+//  counts (may be NULL): int64 {rows counted, top-1 hits, top-k hits, batches} += ...
+//  loss_acc (may be NULL): float64 {sum of batch_loss * B, sum of B} += ..., written by one thread per launch and level
+// Rows whose label is outside [0, classes) or whose scores are NaN are left out of confusion and counts[0..2].
+constexpr int EVAL_TOP_K_MAX = 8;
+struct EvalLevel { BlendCeArgs ce; float* probs; long long* top_idx; float* top_score;
+                   long long* confusion; long long* counts; double* loss_acc; int top_k; };
+struct EvalMulti { EvalLevel lv[BLEND_CE_MULTI_MAX]; int n; };
+int launch_eval_metrics_multi(const EvalMulti& m, hipStream_t st);
 
 }  // namespace dta

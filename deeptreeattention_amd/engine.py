@@ -31,7 +31,111 @@ def _aligned_offsets(params):
     return offs, off
 
 
-class FusedTrainer:
+def metrics_from_accumulators(confusion, counts, loss_acc):
+    """The figures of one level's validation epoch from the accumulators dta_multistage_validate / dta_eval_metrics add to
+    (NumPy arrays on the host): confusion int64 [classes, classes] (rows = label, columns = top-1 class), counts int64
+    {rows, top-1 hits, top-k hits, batches}, loss_acc float64 {sum of batch_loss * batch size, sum of batch sizes}.
+    Returns {"val_loss", "micro", "macro", "top_k", "accuracy", "precision", "confusion", "rows"}: val_loss is weighted by
+    batch size (as Lightning weights a logged batch value; NaN when no batch was seen), top_k = top-k hits / rows, the rest
+    is hierarchy.scores_from_confusion's."""
+    import numpy as np
+    from .hierarchy import scores_from_confusion
+    confusion = np.asarray(confusion, dtype=np.int64)
+    counts = np.asarray(counts, dtype=np.int64)
+    loss_acc = np.asarray(loss_acc, dtype=np.float64)
+    out = scores_from_confusion(confusion)
+    rows = int(counts[0])
+    out["val_loss"] = float(loss_acc[0] / loss_acc[1]) if loss_acc[1] > 0 else float("nan")
+    out["top_k"] = float(counts[2]) / rows if rows > 0 else 0.0
+    out["confusion"] = confusion
+    out["rows"] = rows
+    return out
+
+
+class EvalAccumulators:
+    """The epoch accumulators of one or more levels as ONE flat device buffer of 8-byte words, so that the end of a
+    validation epoch is one device-to-host copy: per level confusion int64 [classes, classes], counts int64 [4], loss_acc
+    float64 [2] (views of the buffer, handed to the C ABI as dta_eval_level's last three pointers)."""
+
+    def __init__(self, classes, device):
+        self.classes = [int(c) for c in classes]
+        self.flat = torch.zeros(sum(c * c + 6 for c in self.classes), dtype=torch.int64, device=device)
+        self.confusion, self.counts, self.loss_acc, self._spans = [], [], [], []
+        off = 0
+        for c in self.classes:
+            self.confusion.append(self.flat[off:off + c * c].view(c, c))
+            self.counts.append(self.flat[off + c * c:off + c * c + 4])
+            self.loss_acc.append(self.flat[off + c * c + 4:off + c * c + 6].view(torch.float64))
+            self._spans.append(off)
+            off += c * c + 6
+
+    def level(self, l, probs, top_idx, top_score, top_k):
+        """dta_eval_level of level l for one batch's output tensors."""
+        top_k = int(top_k)
+        if not 1 <= top_k <= _lib.EVAL_TOP_K_MAX:
+            raise ValueError("top_k must be 1..{}, got {}".format(_lib.EVAL_TOP_K_MAX, top_k))
+        return _lib.EvalLevel(_lib.ptr(probs), top_idx.data_ptr(), top_score.data_ptr(), self.confusion[l].data_ptr(),
+                              self.counts[l].data_ptr(), self.loss_acc[l].data_ptr(), top_k)
+
+    def read(self, reset=True):
+        """ONE device-to-host copy; returns metrics_from_accumulators(...) per level."""
+        host = self.flat.cpu().numpy()
+        if reset:
+            self.flat.zero_()
+        out = []
+        for c, off in zip(self.classes, self._spans):
+            out.append(metrics_from_accumulators(host[off:off + c * c].reshape(c, c).copy(), host[off + c * c:off + c * c + 4],
+                                                 host[off + c * c + 4:off + c * c + 6].view("float64")))
+        return out
+
+
+_EPOCH_END_DOC = """Stated convention, not reference parity: torchmetrics is not part of this package's environment, so the
+figures follow hierarchy.scores_from_confusion (a zero denominator gives 0.0; classes without samples are left out of the
+macro mean).  The reference's own validation_epoch_end (multi_stage.py:323-366) passes `preds` and `target` swapped to its
+macro-accuracy call; the figures here are computed with rows = label, columns = prediction."""
+
+
+class _SingleModelMetrics:
+    """validation_step(..., metrics=True) / validation_epoch_end() of the single-model trainers: the batch's scores go through
+    dta_eval_metrics (loss, softmax, top-2 and the metric counts in ONE launch), which adds to device accumulators."""
+
+    def _metrics_step(self, scores, y, weight, top_k, device):
+        L = _lib.lib()
+        B, classes = scores.shape
+        acc = self.__dict__.get("_eval_acc")
+        if acc is None or acc.classes != [classes]:
+            acc = self._eval_acc = EvalAccumulators([classes], device)
+            self._eval_scratch = {}
+        scratch = self._eval_scratch.get(B)
+        if scratch is None:
+            if len(self._eval_scratch) >= 2:
+                self._eval_scratch.pop(next(iter(self._eval_scratch)))
+            scratch = self._eval_scratch[B] = torch.zeros(B + 2, dtype=torch.float32, device=device)
+        self.val_probs = torch.empty(B, classes, dtype=torch.float32, device=device)
+        self.val_top_idx = torch.empty(B, 2, dtype=torch.int64, device=device)
+        self.val_top_score = torch.empty(B, 2, dtype=torch.float32, device=device)
+        loss = torch.empty((), dtype=torch.float32, device=device)
+        ev = acc.level(0, self.val_probs, self.val_top_idx, self.val_top_score, top_k)
+        scores = scores.contiguous()
+        _lib.check(L.dta_eval_metrics(_lib.ptr(scores), _lib.ptr(y), _lib.ptr(weight), B, classes, _lib.ptr(loss), _lib.ptr(scratch),
+                                      C.byref(ev), _lib.current_stream_ptr()), "dta_eval_metrics")
+        self._eval_live = (scores, y)
+        return loss
+
+    def validation_epoch_end(self, reset=True):
+        """The validation epoch's figures from the device accumulators the metrics=True validation steps added to (ONE
+        device-to-host copy): {"val_loss" (weighted by batch size), "micro", "macro", "top_k", "accuracy", "precision",
+        "confusion", "rows"} (reference main.py:96-133).  reset: start a new epoch.
+        """
+        acc = self.__dict__.get("_eval_acc")
+        if acc is None:
+            raise RuntimeError("validation_epoch_end: no validation_step(..., metrics=True) has run")
+        return acc.read(reset)[0]
+
+    validation_epoch_end.__doc__ += _EPOCH_END_DOC
+
+
+class FusedTrainer(_SingleModelMetrics):
     """Owns flat fp32 parameter / gradient / Adam-moment buffers; the model's Parameters become views of the
     flat parameter buffer (state_dict keys and shapes are unchanged).
 
@@ -606,10 +710,15 @@ class FusedTrainer:
         individual, inputs, y = batch
         return self.train_step(inputs["HSI"], y)
 
-    def validation_step(self, batch, batch_idx=0):
-        """TreeModel.validation_step (src/main.py:82-94): forward + weighted CE, no update."""
+    def validation_step(self, batch, batch_idx=0, metrics=False, top_k=1):
+        """TreeModel.validation_step (src/main.py:82-94): forward + weighted CE, no update.  metrics=True: the loss, the
+        softmax (self.val_probs), the top-2 and the metric collection's counts (main.py:53-61: micro / macro / top-k accuracy)
+        in one more launch that adds to the epoch accumulators validation_epoch_end() reads."""
         individual, inputs, y = batch
-        return self.forward_loss(inputs["HSI"], y)[1]
+        if not metrics:
+            return self.forward_loss(inputs["HSI"], y)[1]
+        logits = self.forward_loss(inputs["HSI"], y)[0]
+        return self._metrics_step(logits, self._labels(y), self.loss_weight, top_k, self.device)
 
     def forward_loss(self, x, y):
         """Forward + loss only (validation_step, reference src/main.py:82-94); returns fresh (logits, loss) tensors."""
@@ -622,7 +731,7 @@ class FusedTrainer:
         return logits.clone(), loss
 
 
-class EnsembleTrainer:
+class EnsembleTrainer(_SingleModelMetrics):
     """Fused train step of the year ensemble (reference src/models/year.py:9-33) as the reference's MultiStage loop
     drives one level of it (src/models/multi_stage.py:277-288 training_step, :258-275 one Adam per level):
     scores = mean over the kept years of each year's last-head scores, loss = weighted CE, backward, Adam.
@@ -1168,6 +1277,15 @@ class EnsembleTrainer:
             self._forward(images, self._kept(images, present), y, False)
         return self.scores.clone(), self.loss
 
+    def validation_step(self, batch, batch_idx=0, metrics=False, top_k=1, present=None):
+        """One level's validation_step (multi_stage.py:290-304) on batch = (individual, {"HSI": [year tensors]}, labels);
+        returns the loss.  metrics=True: loss, softmax, top-2 and metric counts through dta_eval_metrics (see FusedTrainer)."""
+        individual, inputs, y = batch
+        scores, loss = self.forward_loss(inputs["HSI"], y, present)
+        if not metrics:
+            return loss
+        return self._metrics_step(scores, self.years[0]._labels(y), self.loss_weight, top_k, self.device)
+
 
 class MultiStageTrainer:
     """Step driver of the reference's hierarchical model (src/models/multi_stage.py): one year ensemble, one class
@@ -1326,6 +1444,155 @@ class MultiStageTrainer:
         scores, loss = self.levels[dataloader_idx].forward_loss(inputs["HSI"], y, present)
         return {"individual": individual, "yhat": torch.softmax(scores, dim=1), "label": y, "val_loss": loss}
 
+    # ---- validation of every level in ONE launch chain (multi_stage.py:290-304 per level and batch; :323-366 per epoch) ----
+    def _val_plan(self, shapes):
+        """Chains of a validation batch: the present levels grouped by (input shape, precision), each group cut on level
+        boundaries into runs of at most DTA_MAX_LEVELS levels and DTA_MAX_YEARS networks."""
+        groups = {}
+        for l, key in shapes:
+            groups.setdefault(key, []).append(l)
+        chains = []
+        for ls in groups.values():
+            cur, n = [], 0
+            for l in ls:
+                k = len(self.levels[l].years)
+                if cur and (n + k > _lib.MAX_YEARS or len(cur) >= _lib.MAX_LEVELS):
+                    chains.append(cur)
+                    cur, n = [], 0
+                cur.append(l)
+                n += k
+            chains.append(cur)
+        return chains
+
+    def validation_step_all(self, batches, batch_idx=0, present=None, top_k=1):
+        """validation_step of EVERY level on its own batch (the reference's validation loaders differ per level,
+        multi_stage.py:231-246): batches[l] = (individual, {"HSI": [year tensors]}, labels), or None for a level whose loader
+        is exhausted.  Levels whose batches have the same shape share ONE launch chain -- the eval-mode forward of their
+        levels x years networks and ONE epilogue launch for every level's loss, softmax, top-2 and metric counts
+        (dta_multistage_validate); a level with another shape (a short last batch) runs as a chain of its own through the same
+        call, and more than DTA_MAX_YEARS networks are cut on level boundaries (5 levels x 4 years: two chains).  Always
+        eval-mode BatchNorm (running statistics, nothing updated), whatever the modules' `training` flags say; they are left
+        alone.  present: None (missing years decided on the device, no host synchronisation) or one list of booleans per level.
+        Returns, per level, the dict validation_step returns ({"individual", "yhat", "label", "val_loss"}; None for an absent
+        level); the call adds to the epoch accumulators validation_epoch_end() reads.  The last call's top-2 tensors stay in
+        self.val_top_idx[l] / self.val_top_score[l]; self.val_chains_last says how many chains it took, self.val_batched_last
+        whether it was one."""
+        nl = len(self.levels)
+        if len(batches) != nl:
+            raise ValueError("expected one batch (or None) per level ({}), got {}".format(nl, len(batches)))
+        if present is not None and len(present) != nl:
+            raise ValueError("present: one list of year flags per level")
+        if not 1 <= int(top_k) <= _lib.EVAL_TOP_K_MAX:
+            raise ValueError("top_k must be 1..{}, got {}".format(_lib.EVAL_TOP_K_MAX, top_k))
+        here = [l for l in range(nl) if batches[l] is not None]
+        if not here:
+            raise ValueError("validation_step_all: no level brought a batch")
+        xs_levels, shapes = {}, []
+        for l in here:         # every argument is checked before anything is launched
+            t = self.levels[l]
+            images = batches[l][1]["HSI"]
+            if len(images) != len(t.years):
+                raise ValueError("level {}: expected one image tensor per year ({}), got {}".format(l, len(t.years), len(images)))
+            if len(t.years) > _lib.MAX_YEARS:
+                raise RuntimeError("validation_step_all: at most {} years per level".format(_lib.MAX_YEARS))
+            xs = [H._check_input(x) for x in images]
+            if any(x.shape != xs[0].shape for x in xs):
+                raise ValueError("all years of a batch must have the same shape")
+            if batches[l][2].shape[0] != xs[0].shape[0]:
+                raise ValueError("level {}: one label per crop".format(l))
+            precs = {m.precision for m in t.model.year_models}
+            if len(precs) != 1:
+                raise ValueError("level {}: its years must run in one precision".format(l))
+            xs_levels[l] = xs
+            shapes.append((l, (tuple(xs[0].shape), precs.pop())))
+        if self.__dict__.get("_val_acc") is None:
+            self._val_acc = EvalAccumulators([t.model.year_models[0]._classes for t in self.levels], self.levels[0].device)
+            self.val_top_idx, self.val_top_score = [None] * nl, [None] * nl
+            self._val_cache = {}
+        out = [None] * nl
+        chains = self._val_plan(shapes)
+        live = []
+        for chain in chains:
+            live.append(self._validate_chain(chain, batches, xs_levels, present, top_k, out))
+        self._val_live = live      # inputs and labels stay referenced until the launches are enqueued
+        self.val_chains_last = len(chains)
+        self.val_batched_last = len(chains) == 1
+        return out
+
+    def _validate_chain(self, chain, batches, xs_levels, present, top_k, out):
+        L = _lib.lib()
+        st = _lib.current_stream_ptr()
+        dev = self.levels[0].device
+        x0 = xs_levels[chain[0]][0]
+        B, bands, Hh, Ww = x0.shape
+        nets, xptr, lv, ev, live = [], [], [], [], []
+        for l in chain:
+            t = self.levels[l]
+            if present is None:
+                kept = list(range(len(t.years)))
+            else:
+                kept = [i for i, k in enumerate(present[l]) if k]
+                if len(present[l]) != len(t.years) or not kept:
+                    raise RuntimeError("level {}: present needs one flag per year and at least one kept year (year.py:33)".format(l))
+            y = t.years[0]._labels(batches[l][2])
+            classes = t.model.year_models[0]._classes
+            first = len(nets)
+            for i in kept:
+                t.years[i]._describe(xs_levels[l][i])       # (the pointer tables; the descriptor below is this call's own)
+                nets.append(t.years[i].nets[0]); xptr.append(xs_levels[l][i].data_ptr())
+            scratch = t.__dict__.setdefault("_val_scratch", {})
+            if B not in scratch:
+                if len(scratch) >= 2:
+                    scratch.pop(next(iter(scratch)))
+                scratch[B] = torch.zeros(B + 2, dtype=torch.float32, device=dev)      # (last word: block counter)
+            probs = torch.empty(B, classes, dtype=torch.float32, device=dev)          # fresh: handed to the caller
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            self.val_top_idx[l] = torch.empty(B, 2, dtype=torch.int64, device=dev)
+            self.val_top_score[l] = torch.empty(B, 2, dtype=torch.float32, device=dev)
+            lv.append(_lib.Level(classes, first, len(kept), y.data_ptr(), _lib.ptr(t.loss_weight), None, None, loss.data_ptr(), None,
+                                 scratch[B].data_ptr()))
+            ev.append(self._val_acc.level(l, probs, self.val_top_idx[l], self.val_top_score[l], top_k))
+            live.append((xs_levels[l], y))
+            out[l] = {"individual": batches[l][0], "yhat": probs, "label": batches[l][2], "val_loss": loss}
+        n, nc = len(nets), len(chain)
+        m0 = self.levels[chain[0]].model.year_models[0]
+        desc = _lib.NetDesc(B, bands, Hh, Ww, lv[0].classes, _lib.NET_SPECTRAL, _lib.dtype_code(m0.precision), 0,
+                            4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
+        nets_a = (_lib.SubnetParams * n)(*nets)
+        x_a = (C.c_void_p * n)(*xptr)
+        lv_a = (_lib.Level * nc)(*lv)
+        ev_a = (_lib.EvalLevel * nc)(*ev)
+        key = (tuple(chain), tuple((v.classes, v.count) for v in lv), (B, bands, Hh, Ww), m0.precision)
+        hit = self._val_cache.get(key)
+        if hit is None:
+            nbytes = L.dta_multistage_workspace_bytes(C.byref(desc), nc, lv_a)
+            if nbytes == 0:
+                raise RuntimeError("dta_multistage_workspace_bytes: " + L.dta_last_error().decode())
+            if len(self._val_cache) >= 4:
+                self._val_cache.pop(next(iter(self._val_cache)))
+            # workspace + two banks of year flags (a call writes one and zeroes the other for the next call)
+            hit = self._val_cache[key] = [torch.empty(nbytes, dtype=torch.uint8, device=dev),
+                                          torch.zeros(2, n, dtype=torch.float32, device=dev), 0]
+        gate = None
+        if present is None:
+            hit[2] ^= 1
+            gate = hit[1][hit[2]]
+            _lib.check(L.dta_year_flags(x_a, n, x0.numel(), _lib.ptr(gate), _lib.ptr(hit[1][hit[2] ^ 1]), st), "dta_year_flags")
+        _lib.check(L.dta_multistage_validate(C.byref(desc), nc, lv_a, ev_a, nets_a, x_a, _lib.ptr(gate), _lib.ptr(hit[0]), st),
+                   "dta_multistage_validate")
+        return live
+
+    def validation_epoch_end(self, reset=True):
+        """The validation epoch's figures per level from the device accumulators validation_step_all added to, in ONE
+        device-to-host copy: a list of {"val_loss" (weighted by batch size), "micro", "macro", "top_k", "accuracy",
+        "precision", "confusion", "rows"} (reference multi_stage.py:323-366).  reset: start a new epoch.
+        """
+        if self.__dict__.get("_val_acc") is None:
+            raise RuntimeError("validation_epoch_end: no validation_step_all has run")
+        return self._val_acc.read(reset)
+
+    validation_epoch_end.__doc__ += _EPOCH_END_DOC
+
     def predict_step(self, batch, batch_idx=0, present=None):
         """multi_stage.py:306-318: every level's softmax scores for the same crops: ONE eval-mode launch chain over the
         levels x years networks (MultiStagePredictor; a cached Predictor per level when they cannot share a chain); the year
@@ -1370,7 +1637,7 @@ class MultiStageTrainer:
         return (individual,) + tuple(t.clone() for t in ens)
 
 
-class MetadataTrainer:
+class MetadataTrainer(_SingleModelMetrics):
     """Fused train step of the site-metadata fusion model (reference src/models/metadata.py): the step
     MetadataModel.training_step defines (:52-63: unweighted F.cross_entropy(model(images, site), y)) with Adam.
     The HSI branch (Hang2020, >99.9 % of the work) runs through the fused C-ABI pieces on flat buffers; the 16-wide
@@ -1641,8 +1908,9 @@ class MetadataTrainer:
         individual, inputs, y = batch
         return self.train_step(inputs["HSI"], inputs["site"], y)
 
-    def validation_step(self, batch, batch_idx=0):
-        """metadata.py:65-83: forward + unweighted CE, no update."""
+    def validation_step(self, batch, batch_idx=0, metrics=False, top_k=1):
+        """metadata.py:65-83: forward + unweighted CE, no update.  metrics=True: the loss, softmax, top-2 and the metric counts
+        of the fused scores through dta_eval_metrics (see FusedTrainer.validation_step)."""
         individual, inputs, y = batch
         with torch.no_grad():
             scores = self.sensor._forward_scores(inputs["HSI"])
@@ -1650,8 +1918,11 @@ class MetadataTrainer:
                 site = inputs["site"]
                 site = site if (site.dtype == torch.int64 and site.is_cuda) else site.to(self.sensor.device, torch.int64)
                 out, _ = self._native_forward(scores, site.contiguous(), False)
-                return torch.nn.functional.cross_entropy(out, self.sensor._labels(y))
-            return torch.nn.functional.cross_entropy(self._head(scores, inputs["site"]), self.sensor._labels(y))
+            else:
+                out = self._head(scores, inputs["site"])
+            if metrics:
+                return self._metrics_step(out.float(), self.sensor._labels(y), None, top_k, self.sensor.device)
+            return torch.nn.functional.cross_entropy(out, self.sensor._labels(y))
 
 
 class Predictor:

@@ -12,6 +12,8 @@ Lightning itself is out of scope; what a user of the hot path need
   * `fit`                   - epochs of `training_step` / `validation_step` + the scheduler, as Trainer.fit runs them;
   * `fit_multistage`        - the same for the reference's MultiStage module (train.py:75-100): every level of a batch in one
                               launch chain, per-level validation loaders and plateau schedulers.
+  * `validate` / `validate_multistage` - the validation half of an epoch as one function, with the metric collection the
+                              reference logs there (main.py:53-61, :96-133; multi_stage.py:20-28, :323-366) counted on the device;
   * `predict_multistage`    - the prediction loop of src/predict.py:140-151 for a MultiStage module, ending in ONE species label
                               per crop (multi_stage.py:368-434) and, with labels, the confusion matrix of the run.
 No arithmetic happens here; every step is the HIP path behind `engine.FusedTrainer` and friends.
@@ -119,17 +121,69 @@ class SyntheticTreeDataset:
             yield [self.individuals[int(i)] for i in sel.tolist()], inputs, self.labels[sel]
 
 
-def fit(trainer, train_data, val_data=None, epochs=1, batch_size=64, scheduler=None, shuffle=True, log=None):
+def validate(trainer, data, batch_size=64, top_k=1):
+    """The validation half of an epoch for a single-model trainer (FusedTrainer / EnsembleTrainer / MetadataTrainer): eval-mode
+    `validation_step(batch, i, metrics=True)` on every batch of `data.loader(batch_size)` -- loss, softmax, top-2 and the
+    reference's metric collection (main.py:53-61) in one launch behind the forward, accumulated on the device -- then ONE
+    device-to-host copy: returns `trainer.validation_epoch_end()`'s dict ({"val_loss" weighted by batch size, "micro",
+    "macro", "top_k", "accuracy", "precision", "confusion", "rows"})."""
+    model = getattr(trainer, "model", None)
+    was_training = bool(model.training) if model is not None else False
+    if model is not None:
+        model.eval()                 # Lightning's validation loop: running BatchNorm statistics, no updates
+    try:
+        n = 0
+        for i, b in enumerate(data.loader(batch_size)):
+            trainer.validation_step(b, i, metrics=True, top_k=top_k)
+            n += 1
+    finally:
+        if model is not None and was_training:
+            model.train()
+    if n == 0:
+        raise ValueError("validate: the dataset yields no batch")
+    return trainer.validation_epoch_end()
+
+
+def validate_multistage(trainer, data, batch_size=128, top_k=1):
+    """The validation half of an epoch for an engine.MultiStageTrainer: the levels' own validation loaders
+    (multi_stage.py:231-246) zipped WITHOUT cycling -- every validation batch is seen once; a level whose loader ran out
+    brings None -- and `validation_step_all` on each list of batches (one launch chain for the levels whose batches agree in
+    shape), then ONE device-to-host copy: returns `trainer.validation_epoch_end()`'s list of per-level dicts.  The modules'
+    train / eval flags are not touched (the chain always runs eval-mode BatchNorm)."""
+    nl = len(trainer.levels)
+    if len(data) != nl:
+        raise ValueError("one dataset per level ({})".format(nl))
+    its = [iter(d.loader(batch_size)) for d in data]
+    i = 0
+    while True:
+        batches = [next(it, None) for it in its]
+        if all(b is None for b in batches):
+            break
+        trainer.validation_step_all(batches, i, None, top_k)
+        i += 1
+    if i == 0:
+        raise ValueError("validate_multistage: the datasets yield no batch")
+    return trainer.validation_epoch_end()
+
+
+def fit(trainer, train_data, val_data=None, epochs=1, batch_size=64, scheduler=None, shuffle=True, log=None, metrics=False):
     """Epoch loop as Lightning's Trainer.fit runs the reference's LightningModules: `training_step(batch, i)` on every
     training batch, then `validation_step(batch, i)` on every validation batch, `val_loss` = mean of the batch losses
     (what `self.log("val_loss", loss)` aggregates, src/main.py:90), then the plateau scheduler.  `trainer` is a
     FusedTrainer / MetadataTrainer (or anything with the two step methods).  Losses stay on the device inside an epoch
-    (one host read per epoch).  Returns a list of {"epoch", "train_loss", "val_loss", "lr"} records."""
+    (one host read per epoch).  Returns a list of {"epoch", "train_loss", "val_loss", "lr"} records.
+    metrics=True: the validation half is `validate` -- `val_loss` is then weighted by batch size (a short last batch counts
+    for its rows, as in Lightning), the scheduler monitors that, and the record gains "val_metrics"."""
     history = []
     for epoch in range(int(epochs)):
         tl = [trainer.training_step(b, i) for i, b in enumerate(train_data.loader(batch_size, shuffle, seed=epoch))]
         rec = {"epoch": epoch, "train_loss": float(torch.stack([t.reshape(()) for t in tl]).mean()), "val_loss": None}
-        if val_data is not None:
+        if val_data is not None and metrics:
+            rec["val_metrics"] = validate(trainer, val_data, batch_size)
+            rec["val_loss"] = rec["val_metrics"]["val_loss"]
+            if scheduler is not None:
+                scheduler.step(rec["val_loss"])
+        elif val_data is not None:
             model = getattr(trainer, "model", None)
             was_training = bool(model.training) if model is not None else False
             if model is not None:
@@ -149,7 +203,8 @@ def fit(trainer, train_data, val_data=None, epochs=1, batch_size=64, scheduler=N
     return history
 
 
-def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128, schedulers=None, shuffle=True, log=None):
+def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128, schedulers=None, shuffle=True, log=None,
+                   metrics=False):
     """The epoch loop `train.py:75-100` runs for the reference's MultiStage module: `train_dataloader()` returns one loader
     per level (multi_stage.py:212-229), Lightning zips them into a list-of-batches and calls `training_step` once per
     optimizer -- here ALL levels of a batch are one launch chain (`MultiStageTrainer.training_step_all`; a level whose
@@ -158,7 +213,9 @@ def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128,
     losses, and one plateau scheduler per level monitoring it (multi_stage.py:258-275).
     trainer: engine.MultiStageTrainer; train_data / val_data: one SyntheticTreeDataset(years=...) (or anything with
     `.loader(batch_size, shuffle, seed)`) per level; schedulers: one PlateauScheduler per level (on `trainer.levels[l]`) or
-    None.  Returns a list of {"epoch", "train_loss": [...], "val_loss": [...], "lr": [...]} records."""
+    None.  Returns a list of {"epoch", "train_loss": [...], "val_loss": [...], "lr": [...]} records.
+    metrics=True: the validation half is `validate_multistage` (all levels of a validation batch in one launch chain);
+    `val_loss` is then weighted by batch size, the schedulers monitor that, and the record gains "val_metrics" (per level)."""
     import itertools
     nl = len(trainer.levels)
     if len(train_data) != nl or (val_data is not None and len(val_data) != nl):
@@ -173,7 +230,14 @@ def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128,
             for l, loss in enumerate(trainer.training_step_all(batch, i)):
                 sums[l].append(loss.reshape(()))
         rec = {"epoch": epoch, "train_loss": [float(torch.stack(s).mean()) for s in sums], "val_loss": None}
-        if val_data is not None:
+        if val_data is not None and metrics:
+            rec["val_metrics"] = validate_multistage(trainer, val_data, batch_size)
+            rec["val_loss"] = [m["val_loss"] for m in rec["val_metrics"]]
+            if schedulers is not None:
+                for l, sch in enumerate(schedulers):
+                    if sch is not None:
+                        sch.step(rec["val_loss"][l])
+        elif val_data is not None:
             models = [t.model for t in trainer.levels]
             was = [bool(m.training) for m in models]
             for m in models:

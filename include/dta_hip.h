@@ -394,6 +394,36 @@ int dta_hierarchy_resolve(int levels, const long long* const* top_idx, const flo
                           const dta_hierarchy* table, long long* ens_label, float* ens_score, int* ens_level,
                           const long long* labels, long long* confusion, void* stream);
 
+/* ---- Validation on the device (reference multi_stage.py:290-304 validation_step: weighted cross-entropy + softmax + the
+ * metric collection of :20-28 / main.py:53-61; :323-366 and main.py:96-133 validation_epoch_end).  ONE launch per batch does,
+ * for every level, the loss, the softmax, the top-2 and the metric counts, and ADDS to epoch accumulators, so that an epoch
+ * needs no launch and no host read of its own:
+ *  confusion : int64 [classes][classes], confusion[label][top-1 class] += 1 (64-bit integer atomics: order-independent)
+ *  counts    : int64 {rows counted, top-1 hits, top-k hits, batches}
+ *  loss_acc  : float64 {sum over batches of batch_loss * batch, sum of batch}: the epoch loss weighted by batch size is
+ *              loss_acc[0] / loss_acc[1]; one writer per call and level, no floating-point atomics (reruns are bit-identical)
+ * The caller zeroes the accumulators at the start of an epoch.  A row whose label is outside [0, classes) or whose scores
+ * are NaN is left out of confusion and counts[0..2].  top_k: 1..DTA_EVAL_TOP_K_MAX; a tie goes to the lower class index, as
+ * in the top-2 outputs. */
+#define DTA_EVAL_TOP_K_MAX 8
+typedef struct dta_eval_level {
+  float* probs; long long* top_idx; float* top_score;   /* per-batch outputs [batch][classes], [batch][2], [batch][2]; probs may be NULL */
+  long long* confusion; long long* counts; double* loss_acc;   /* accumulators, may each be NULL */
+  int top_k;
+} dta_eval_level;
+/* Eval-mode forward of the levels x kept-years networks + the epilogue above, ONE chain.  d->training must be 0 and
+ * d->heads_mask carry DTA_FORWARD_ONLY; DTA_REUSE_PACKED is refused (validation follows weight updates).  Of lv[l], labels,
+ * loss and scratch are required, weight / mean_scores / kept are optional, dscore is not written.  Each level brings its own
+ * inputs and labels (x: one tensor per network, as for dta_multistage_forward_loss).  Every argument is checked on the host
+ * before anything is launched. */
+int dta_multistage_validate(const dta_net_desc* d, int levels, const dta_level* lv, const dta_eval_level* ev,
+                            const dta_subnet_params* nets, const float* const* x, const float* gate,
+                            void* workspace, void* stream);
+/* The epilogue alone on [batch][classes] scores (single models: Hang2020, metadata fusion, one year ensemble).
+ * weight may be NULL (= ones); loss: device scalar; scratch: batch + 2 floats, last word zero on entry and left zero. */
+int dta_eval_metrics(const float* scores, const long long* labels, const float* weight, int batch, int classes,
+                     float* loss, float* scratch, const dta_eval_level* ev, void* stream);
+
 /* ---- Peer gradient exchange: data-parallel training with one process per GPU of ONE node (reference train.py:89-98:
  * Lightning DDP all-reduces every parameter's gradient between loss.backward() and optimizer.step()).  Here the sum over
  * ranks and the Adam step are ONE launch on the caller's compute stream: every rank pulls its shard of all ranks'
