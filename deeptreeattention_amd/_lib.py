@@ -266,6 +266,14 @@ def lib():
         L.dta_linear_backward.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         L.dta_softmax_top2.restype = C.c_int
         L.dta_softmax_top2.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.dta_raster_normalise.restype = C.c_int
+        L.dta_raster_normalise.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.dta_gather_windows.restype = C.c_int
+        L.dta_gather_windows.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+        L.dta_gather_windows_tiles.restype = C.c_int
+        L.dta_gather_windows_tiles.argtypes = L.dta_gather_windows.argtypes
+        L.dta_crown_reduce.restype = C.c_int
+        L.dta_crown_reduce.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

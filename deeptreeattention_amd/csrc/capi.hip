@@ -1586,4 +1586,50 @@ int dta_adam_step_dp(float* p, float* g, float* m, float* v, size_t n, double* a
                         step, lr, beta1, beta2, eps, grad_scale, stream, nullptr, nullptr, alpha_g_f32);
 }
 
+// ---- dense per-pixel window prediction (dense.hip) ----
+int dta_raster_normalise(const void* raw, int bands_raw, int height, int width, int clip, int dtype, int tiles, void* out,
+                         void* stream) {
+  if (!raw || !out) { dta_set_error("dta_raster_normalise: null argument"); return 1; }
+  if (bands_raw < 1 || height < 1 || width < 1 || clip < 0) { dta_set_error("dta_raster_normalise: bad shape: bands=%d H=%d W=%d clip=%d", bands_raw, height, width, clip); return 1; }
+  RasterArgs a;
+  a.raw = raw; a.out = out; a.P = (long long)height * width; a.tiles = tiles != 0;
+  a.c0 = bands_raw > 3 ? clip : 0;      // reference utils.py:40-42: bands are dropped only when there are more than 3
+  a.C = dta_preprocess_out_bands(bands_raw, clip);
+  if (a.C < 1) { dta_set_error("dta_raster_normalise: %d bands leave nothing after dropping 2 x %d", bands_raw, clip); return 1; }
+  if (a.tiles && ((uintptr_t)out & 15)) { dta_set_error("dta_raster_normalise: the chunk form needs a 16-byte aligned buffer"); return 1; }
+  return launch_raster_normalise(a, dtype, (hipStream_t)stream);
+}
+
+static int gather_args(const char* who, const void* raster, int bands, int height, int width, const int* origins, int n,
+                       int size, void* out, GatherArgs* a) {
+  if (!raster || !origins || !out) { dta_set_error("%s: null argument", who); return 1; }
+  if (bands < 1 || height < 1 || width < 1 || n < 1) { dta_set_error("%s: bad shape: bands=%d H=%d W=%d n=%d", who, bands, height, width, n); return 1; }
+  if (size < 4 || size > 253) { dta_set_error("%s: window side %d outside 4..253 (what the networks take)", who, size); return 1; }
+  if (((uintptr_t)raster & 15) || ((uintptr_t)out & 15)) { dta_set_error("%s: raster and output must be 16-byte aligned", who); return 1; }
+  a->raster = raster; a->origins = origins; a->out = out; a->N = n; a->C = bands; a->H = height; a->W = width; a->S = size;
+  return 0;
+}
+int dta_gather_windows(const float* raster, int bands, int height, int width, const int* origins, int n, int size,
+                       float* out, void* stream) {
+  GatherArgs a;
+  if (gather_args("dta_gather_windows", raster, bands, height, width, origins, n, size, out, &a)) return 1;
+  return launch_gather_windows(a, (hipStream_t)stream);
+}
+int dta_gather_windows_tiles(const void* raster, int bands, int height, int width, const int* origins, int n, int size,
+                             void* tiles, void* stream) {
+  GatherArgs a;
+  if (gather_args("dta_gather_windows_tiles", raster, bands, height, width, origins, n, size, tiles, &a)) return 1;
+  return launch_gather_windows_tiles(a, (hipStream_t)stream);
+}
+
+int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns, int classes, float* mean,
+                     long long* top_idx, float* top_score, int* count, void* stream) {
+  if (!probs || !offsets || !mean || !top_idx || !top_score || !count) { dta_set_error("dta_crown_reduce: null argument"); return 1; }
+  if (n_crowns < 1 || classes < 1) { dta_set_error("dta_crown_reduce: bad shape: crowns=%d classes=%d", n_crowns, classes); return 1; }
+  CrownArgs a;
+  a.probs = probs; a.offsets = offsets; a.n_crowns = n_crowns; a.classes = classes;
+  a.mean = mean; a.top_idx = top_idx; a.top_score = top_score; a.count = count;
+  return launch_crown_reduce(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

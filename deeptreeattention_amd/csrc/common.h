@@ -149,6 +149,20 @@ __device__ __forceinline__ float block_sum256(float v, float* scratch) {
   return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
+// The scaling arithmetic of the per-pixel min-max (k_preprocess_crops*, preprocess.hip; k_raster_normalise, dense.hip).
+// THE CONTRACT between the two files: the window of the normalised raster equals the normalised window bit for bit only
+// while both use these very definitions (and `#pragma clang fp contract(off)`); change them here, for both, or not at all.
+// x * s rounded to float32 on its own: the empty asm makes the product opaque, so no later add can be fused into it
+__device__ __forceinline__ float mul_rounded(float x, float s) {
+  float p = x * s;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+// a raw raster / crop element as float32
+__device__ __forceinline__ float to_f(float v) { return v; }
+__device__ __forceinline__ float to_f(short v) { return (float)v; }
+__device__ __forceinline__ float to_f(unsigned char v) { return (float)v; }
+
 }  // namespace dta
 
 // hipFuncSetAttribute is a per-device setting: a launch site remembers per device ordinal whether it has made it (one

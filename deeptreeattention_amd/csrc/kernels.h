@@ -676,4 +676,18 @@ struct EvalLevel { BlendCeArgs ce; float* probs; long long* top_idx; float* top_
 struct EvalMulti { EvalLevel lv[BLEND_CE_MULTI_MAX]; int n; };
 int launch_eval_metrics_multi(const EvalMulti& m, hipStream_t st);
 
+// ---- dense.hip: per-pixel window prediction over a resident raster ----------------------------------
+// raw [Craw][P] (band-first, P = H * W pixels) -> bands c0 .. c0 + C - 1, min-max per pixel over them;
+// out: float32 [C][P], or (tiles) bf16 [ceil(C / 16)][P][16]
+struct RasterArgs { const void* raw; void* out; long long P; int c0, C, tiles; };
+int launch_raster_normalise(const RasterArgs& a, int dtype, hipStream_t st);      // dtype: DTA_CROP_F32 / I16 / U8
+// origins [N][2] int32 (row, col) of each window's top-left corner, anywhere (outside the raster: zeros)
+struct GatherArgs { const void* raster; const int* origins; void* out; int N, C, H, W, S; };
+int launch_gather_windows(const GatherArgs& a, hipStream_t st);          // float32 [C][H][W] -> float32 [N][C][S][S]
+int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st);    // bf16 chunks -> bf16 [N][ceil(C / 16)][S * S][16]
+// probs [rows][classes], crown k = rows offsets[k] .. offsets[k + 1]
+struct CrownArgs { const float* probs; const long long* offsets; int n_crowns, classes;
+                   float* mean; long long* top_idx; float* top_score; int* count; };
+int launch_crown_reduce(const CrownArgs& a, hipStream_t st);
+
 }  // namespace dta

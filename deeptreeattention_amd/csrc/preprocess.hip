@@ -12,28 +12,17 @@
 
 // Bit-exactness with the reference needs the multiply and the add of the scaling rounded SEPARATELY (NumPy does
 // `X *= scale; X += min`): no fused multiply-add in this file (hipcc contracts by default, and HIP's __fmul_rn /
-// __fadd_rn are plain operators that the contraction sees through; see mul_rounded below).
+// __fadd_rn are plain operators that the contraction sees through; see mul_rounded in common.h).
 #pragma clang fp contract(off)
 
 namespace {
 
 using namespace dta;
 
-// x * s rounded to float32 on its own: the empty asm makes the product opaque, so no later add can be fused into it
-__device__ __forceinline__ float mul_rounded(float x, float s) {
-  float p = x * s;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
 struct CropArgs {
   const void* raw; const long long* off; const int* hs; const int* ws; float* out;
   int B, Craw, c0, C, S, flip, pitch, cc, np;   // np: output pixels per workgroup (a crop is split into SS/np workgroups)
 };
-
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(short v) { return (float)v; }
-__device__ __forceinline__ float to_f(unsigned char v) { return (float)v; }
 
 // ATen's nearest-neighbour source index: min(floor(dst * float(in / out)), in - 1)
 __device__ __forceinline__ int nearest_src(int dst, int in, int out) {

@@ -1,0 +1,299 @@
+"""Dense per-pixel window prediction over a hyperspectral raster: the reference's `bounds_to_pixel` (src/patches.py:50-83:
+one 11x11 window per pixel of a crown box, read with boundless=True) followed by `TreeModel.predict_dataloader`
+(src/main.py:165-205), without ever slicing a window on the host.
+
+The reference's preprocessing is per pixel position (drop 10 + 10 bands, min-max over the bands of that pixel,
+src/utils.py:36-57) and an 11x11 window resized to 11x11 with NEAREST is the identity, so the preprocessed window equals
+the window of the preprocessed raster, bit for bit (a zero-filled out-of-bounds pixel stays zero: its range is below
+scikit-learn's "constant" threshold).  Hence:
+
+    DenseRaster          one host-to-device copy of the raw raster and ONE normalise launch (dta_raster_normalise)
+    window_origins       pixel boxes -> window origins + crown offsets (pure host function)
+    DenseRaster.windows  origins -> the float32 batch or the first conv's bf16 tiles (dta_gather_windows[_tiles])
+    predict_windows      gather -> eval forward -> softmax / top-2 per batch, no host synchronisation inside the loop;
+                         with crown offsets also the per-crown mean, top-2 and count (dta_crown_reduce)
+    predict_map          a label map and a score map of a raster region
+
+`gather_windows_np` and `crown_reduce_np` are the written-down meaning of the gather and reduce kernels.
+File reading and georeferencing stay with the caller, as in preprocess.py."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+from .preprocess import PatchTiles, out_bands, _DTYPES
+
+WINDOW = 11     # Hang et al. 2020: one 11x11 window per pixel
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# host definitions
+# ---------------------------------------------------------------------------------------------------------------------
+def window_origins(boxes, anchor="corner", size=WINDOW):
+    """boxes: pixel boxes (row0, col0, row1, col1), half-open.  One window per pixel of each box, row-major within the box.
+    Returns (origins int32 [N, 2] = (row, col) of each window's top-left corner, crown_offsets int64 [len(boxes) + 1]).
+    anchor="corner": the pixel is the window's top-left (the reference's bounds_to_pixel: Window(col_off=col, row_off=row));
+    anchor="center": the pixel is the window's centre (the paper's form): origins shifted by -(size // 2)."""
+    if anchor not in ("corner", "center"):
+        raise ValueError("anchor must be 'corner' or 'center', got {!r}".format(anchor))
+    shift = size // 2 if anchor == "center" else 0
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    parts, offsets = [], np.zeros(len(boxes) + 1, dtype=np.int64)
+    for k, (r0, c0, r1, c1) in enumerate(boxes):
+        h, w = max(int(r1 - r0), 0), max(int(c1 - c0), 0)
+        rr, cc = np.meshgrid(np.arange(r0, r0 + h), np.arange(c0, c0 + w), indexing="ij")
+        parts.append(np.stack([rr.reshape(-1), cc.reshape(-1)], axis=1) - shift)
+        offsets[k + 1] = offsets[k] + h * w
+    origins = np.concatenate(parts, axis=0) if parts else np.zeros((0, 2), dtype=np.int64)
+    return origins.astype(np.int32).reshape(-1, 2), offsets
+
+
+def gather_windows_np(raster_norm, origins, size=WINDOW):
+    """What dta_gather_windows computes: raster_norm [C][H][W] -> [N][C][size][size]; window n covers rows
+    origins[n, 0] .. + size and columns origins[n, 1] .. + size of the raster, positions outside it are zero."""
+    raster_norm = np.asarray(raster_norm)
+    origins = np.asarray(origins).reshape(-1, 2)
+    Cb, Hh, Ww = raster_norm.shape
+    out = np.zeros((len(origins), Cb, size, size), dtype=raster_norm.dtype)
+    for n, (r, c) in enumerate(origins):
+        r, c = int(r), int(c)
+        ra, rb, ca, cb = max(r, 0), min(r + size, Hh), max(c, 0), min(c + size, Ww)
+        if ra < rb and ca < cb:
+            out[n, :, ra - r:rb - r, ca - c:cb - c] = raster_norm[:, ra:rb, ca:cb]
+    return out
+
+
+def crown_reduce_np(probs, offsets):
+    """What dta_crown_reduce computes.  probs [rows][classes] float32, crown k = rows offsets[k] .. offsets[k + 1] - 1.
+    Each class is summed in row order in float32 (one accumulator) and divided by the count; top-2 of the mean with ties to
+    the lower class; an empty crown has count 0, labels -1, scores and mean 0.
+    Returns (mean [n][classes] float32, top_idx [n][2] int64, top_score [n][2] float32, count [n] int32)."""
+    probs = np.asarray(probs, dtype=np.float32)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n, classes = len(offsets) - 1, probs.shape[1]
+    mean = np.zeros((n, classes), dtype=np.float32)
+    top_idx = np.full((n, 2), -1, dtype=np.int64)
+    top_score = np.zeros((n, 2), dtype=np.float32)
+    count = np.zeros(n, dtype=np.int32)
+    for k in range(n):
+        r0, r1 = int(offsets[k]), int(offsets[k + 1])
+        if r1 <= r0:
+            continue
+        acc = np.zeros(classes, dtype=np.float32)
+        for r in range(r0, r1):
+            acc = acc + probs[r]                      # float32, row order
+        m = acc / np.float32(r1 - r0)
+        mean[k], count[k] = m, r1 - r0
+        valid = np.flatnonzero(m > -1.0)              # (NaNs never win, as in dta_softmax_top2)
+        order = valid[np.argsort(-m[valid], kind="stable")][:2]
+        top_idx[k, :len(order)] = order
+        top_score[k, :len(order)] = m[order]
+    return mean, top_idx, top_score, count
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device side
+# ---------------------------------------------------------------------------------------------------------------------
+class DenseRaster:
+    """A raw band-first raster [bands][H][W] (what rasterio's read() returns; int16, uint8 or float32, anything else is
+    converted to float32 as the reference does) copied to the device once and normalised there once: the clipped
+    per-pixel min-max of preprocess.preprocess_batch.  precision="fp32" keeps float32 [C][H][W] (for the float32 gather),
+    "bf16" the first conv's channel chunks [ceil(C / 16)][H * W][16] (for the tile gather; bf16-mode Hang2020)."""
+
+    def __init__(self, raster, clip=10, precision="bf16", device="cuda"):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("deeptreeattention_amd.dense runs on a ROCm device only (no CPU fallback)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if precision not in ("bf16", "fp32"):
+            raise ValueError("precision must be 'bf16' or 'fp32', got {!r}".format(precision))
+        a = raster.detach().cpu().numpy() if isinstance(raster, torch.Tensor) else np.asarray(raster)
+        if a.ndim != 3:
+            raise ValueError("the raster must be a band-first 3-d array")
+        if a.dtype not in _DTYPES:
+            a = a.astype(np.float32)
+        L = _lib.lib()
+        bands_raw, Hh, Ww = a.shape
+        self.bands, self.height, self.width = out_bands(bands_raw, clip), Hh, Ww
+        self.shape = (self.bands, Hh, Ww)
+        self.precision, self.device = precision, dev
+        raw = torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        if precision == "bf16":
+            self.data = torch.empty(((self.bands + 15) // 16) * Hh * Ww * 16, dtype=torch.int16, device=dev)
+        else:
+            self.data = torch.empty(self.bands, Hh, Ww, dtype=torch.float32, device=dev)
+        _lib.check(L.dta_raster_normalise(_lib.ptr(raw), bands_raw, Hh, Ww, clip, _DTYPES[a.dtype], int(precision == "bf16"),
+                                          _lib.ptr(self.data), _lib.current_stream_ptr()), "dta_raster_normalise")
+
+    def float(self):
+        """The normalised raster as a float32 [C][H][W] tensor (bf16 form: the bf16-rounded values)."""
+        if self.precision == "fp32":
+            return self.data
+        t = self.data.view(-1, self.height * self.width, 16).view(torch.bfloat16).float()      # [chunk][pixel][16]
+        return t.permute(0, 2, 1).reshape(-1, self.height, self.width)[:self.bands].contiguous()
+
+    def _origins(self, origins):
+        if isinstance(origins, torch.Tensor):
+            o = origins
+            if o.dtype != torch.int32 or o.device != self.device or not o.is_contiguous():
+                o = o.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            o = torch.from_numpy(np.ascontiguousarray(np.asarray(origins, dtype=np.int32))).to(self.device)
+        if o.dim() != 2 or o.shape[1] != 2 or o.shape[0] < 1:
+            raise ValueError("origins must be a non-empty [N, 2] array of (row, col)")
+        return o
+
+    def windows(self, origins, tiles=False, size=WINDOW, out=None):
+        """origins: [N, 2] int32 (row, col) of each window's top-left corner (host array or device tensor); may hang over
+        the raster's edges (zero fill).  Returns the float32 (N, bands, size, size) batch (an fp32 raster), or with
+        tiles=True a preprocess.PatchTiles (a bf16 raster).  out: the buffer to write (same shape / element count)."""
+        L = _lib.lib()
+        o = self._origins(origins)
+        N = o.shape[0]
+        if tiles:
+            if self.precision != "bf16":
+                raise RuntimeError("tiles=True needs DenseRaster(..., precision='bf16')")
+            numel = N * ((self.bands + 15) // 16) * size * size * 16
+            if out is None:
+                out = torch.empty(numel, dtype=torch.int16, device=self.device)
+            elif out.dtype != torch.int16 or out.numel() != numel or not out.is_contiguous():
+                raise ValueError("out must be a contiguous int16 tensor of {} elements".format(numel))
+            _lib.check(L.dta_gather_windows_tiles(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N,
+                                                  size, _lib.ptr(out), _lib.current_stream_ptr()), "dta_gather_windows_tiles")
+            return PatchTiles(out, N, self.bands, size, size)
+        if self.precision != "fp32":
+            raise RuntimeError("the float32 batch needs DenseRaster(..., precision='fp32')")
+        shape = (N, self.bands, size, size)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of shape {}".format(shape))
+        _lib.check(L.dta_gather_windows(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N, size,
+                                        _lib.ptr(out), _lib.current_stream_ptr()), "dta_gather_windows")
+        return out
+
+
+CrownPredictions = collections.namedtuple("CrownPredictions", "mean top_idx top_score count")
+WindowPredictions = collections.namedtuple("WindowPredictions", "top_idx top_score probs crowns")
+
+
+def crown_reduce(probs, crown_offsets):
+    """dta_crown_reduce on device probabilities [rows][classes] (float32, contiguous): CrownPredictions(mean
+    [n][classes], top_idx [n][2] int64, top_score [n][2], count [n] int32), all on the device."""
+    L = _lib.lib()
+    dev = probs.device
+    if probs.dtype != torch.float32 or probs.dim() != 2 or not probs.is_contiguous():
+        raise ValueError("probs must be a contiguous float32 [rows][classes] tensor")
+    host = crown_offsets.detach().cpu().numpy() if isinstance(crown_offsets, torch.Tensor) else np.asarray(crown_offsets)
+    host = host.astype(np.int64)
+    if host.ndim != 1 or len(host) < 2 or host[0] < 0 or (np.diff(host) < 0).any() or host[-1] > probs.shape[0]:
+        raise ValueError("crown_offsets must be non-decreasing, start at >= 0 and end within the {} rows".format(probs.shape[0]))
+    off = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+    n, classes = len(host) - 1, probs.shape[1]
+    out = CrownPredictions(torch.empty(n, classes, dtype=torch.float32, device=dev),
+                           torch.empty(n, 2, dtype=torch.int64, device=dev),
+                           torch.empty(n, 2, dtype=torch.float32, device=dev),
+                           torch.empty(n, dtype=torch.int32, device=dev))
+    _lib.check(L.dta_crown_reduce(_lib.ptr(probs), _lib.ptr(off), n, classes, _lib.ptr(out.mean), _lib.ptr(out.top_idx),
+                                  _lib.ptr(out.top_score), _lib.ptr(out.count), _lib.current_stream_ptr()), "dta_crown_reduce")
+    return out
+
+
+def _predictor(model_or_predictor):
+    from .engine import Predictor
+    return model_or_predictor if isinstance(model_or_predictor, Predictor) else Predictor(model_or_predictor)
+
+
+def raster_precision(model_or_predictor):
+    """The DenseRaster form the network's route reads: "bf16" for a bf16-mode Hang2020 (tile gather +
+    dta_net_forward_tiles), "fp32" for every other network kind and precision (float32 gather)."""
+    p = _predictor(model_or_predictor)
+    m = p.nets_mod[0]
+    tiles = (not p.ensemble) and m._net_code == _lib.NET_HANG2020 and m.precision == "bf16"
+    return "bf16" if tiles else "fp32"
+
+
+def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False):
+    """Per-window prediction on 11x11 windows (the side every prediction route here is tested at; DenseRaster.windows
+    gathers other sides): walks `origins` in batches of `batch_size` -- gather, the existing eval forward
+    (engine.Predictor), dta_softmax_top2 -- writing top_idx [N, 2] / top_score [N, 2] into preallocated device tensors;
+    nothing inside the loop waits for the device.
+    rasters: a DenseRaster in the form raster_precision() names; for a year.learned_ensemble one per year, None for a
+    missing year (an all-zero batch, reference data.py:295-296).
+    crown_offsets ([n + 1], windows grouped by crown as window_origins returns them): also the per-crown mean probability
+    vector, its top-2 and the window count.  Window probabilities are kept when return_probs or crown_offsets ask for them.
+    Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None)."""
+    L = _lib.lib()
+    pred = _predictor(model_or_predictor)
+    want = raster_precision(pred)
+    size = WINDOW
+    if pred.ensemble:
+        rs = list(rasters)
+        if len(rs) != len(pred.nets_mod):
+            raise ValueError("a {}-year ensemble needs {} rasters (None for a missing year)".format(len(pred.nets_mod), len(pred.nets_mod)))
+    else:
+        rs = [rasters]
+    have = [r for r in rs if r is not None]
+    if not have:
+        raise ValueError("at least one year's raster must be present")
+    r0 = have[0]
+    for r in have:
+        if not isinstance(r, DenseRaster):
+            raise TypeError("rasters must be DenseRaster objects")
+        if r.precision != want:
+            raise RuntimeError("this network reads a DenseRaster(..., precision={!r}) (dense.raster_precision)".format(want))
+        if r.shape != r0.shape:
+            raise ValueError("all years' rasters must share one shape")
+    dev = r0.device
+    o = r0._origins(origins)
+    N, classes = o.shape[0], pred.nets_mod[0]._classes
+    keep = return_probs or crown_offsets is not None
+    top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
+    top_score = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
+    B = min(int(batch_size), N)
+    tiles = want == "bf16"
+    if tiles:
+        per = ((r0.bands + 15) // 16) * size * size * 16
+        bufs = [torch.empty(B * per, dtype=torch.int16, device=dev)]
+    else:
+        per = r0.bands * size * size
+        bufs = [torch.empty(B, r0.bands, size, size, dtype=torch.float32, device=dev) if r is not None else None for r in rs]
+        if any(b is None for b in bufs):
+            zeros = torch.zeros(B, r0.bands, size, size, dtype=torch.float32, device=dev)
+            bufs = [zeros if b is None else b for b in bufs]
+    st = _lib.current_stream_ptr()
+    for n0 in range(0, N, B):
+        n = min(B, N - n0)
+        ob = o[n0:n0 + n]
+        if tiles:
+            x = r0.windows(ob, tiles=True, size=size, out=bufs[0][:n * per])
+        else:
+            xs = [b[:n] if r is None else r.windows(ob, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
+            x = xs if pred.ensemble else xs[0]
+        logits = pred.logits_of(x)
+        _lib.check(L.dta_softmax_top2(_lib.ptr(logits), n, classes, _lib.ptr(probs[n0:n0 + n]) if keep else None,
+                                      _lib.ptr(top_idx[n0:n0 + n]), _lib.ptr(top_score[n0:n0 + n]), st), "dta_softmax_top2")
+    crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
+    return WindowPredictions(top_idx, top_score, probs if return_probs else None, crowns)
+
+
+def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=None, clip=10, batch_size=4096):
+    """Label every pixel of a raster region: rows / cols are half-open (start, stop) pixel ranges (default: the whole
+    raster).  raster: a raw band-first array or a DenseRaster (a list with one per year, None allowed, for an ensemble).
+    Returns (labels [h][w] int64, scores [h][w] float32): the top-1 class of each pixel's window and its probability."""
+    pred = _predictor(model_or_predictor)
+    want = raster_precision(pred)
+
+    def resident(r):
+        return r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision=want, device=pred.device)
+    rs = [resident(r) for r in raster] if pred.ensemble else resident(raster)
+    first = next(r for r in rs if r is not None) if pred.ensemble else rs
+    r0, r1 = rows if rows is not None else (0, first.height)
+    c0, c1 = cols if cols is not None else (0, first.width)
+    origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
+    res = predict_windows(pred, rs, origins, batch_size=batch_size)
+    h, w = r1 - r0, c1 - c0
+    return res.top_idx[:, 0].reshape(h, w), res.top_score[:, 0].reshape(h, w)

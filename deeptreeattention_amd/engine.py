@@ -1933,6 +1933,8 @@ class Predictor:
 
     model: a network of this package (Hang2020, vanilla_CNN; spectral/spatial_network -> last head) or a
     year.learned_ensemble (zero years are skipped as in training: one host transfer per call, or pass `present`).
+    A bf16-mode Hang2020 also takes a preprocess.PatchTiles (the batch already as the first conv's bf16 tiles:
+    dta_net_forward_tiles), with the same scores bit for bit as on the float batch those tiles were rounded from.
     The pointer tables are rebuilt when the batch shape changes; call refresh() after replacing parameter tensors
     (in-place updates, e.g. by FusedTrainer or load_state_dict, need nothing).
     frozen=True (tile prediction with a trained model, reference predict.py:140-151): the conv / attention weight
@@ -2078,7 +2080,16 @@ class Predictor:
                                               _lib.ptr(self.logits), st), "dta_ensemble_forward")
             self._packed = True
             return self.logits
-        x = H._check_input(images)
+        tiles = getattr(images, "tiles", None)   # preprocess.PatchTiles: the input already as the first conv's bf16 tiles
+        if tiles is not None:
+            m0 = self.nets_mod[0]
+            if m0.precision != "bf16" or m0._net_code != _lib.NET_HANG2020:
+                raise RuntimeError("PatchTiles inputs need a bf16-mode Hang2020 (every other network takes the float32 batch)")
+            if tuple(images.shape[2:]) != (11, 11):
+                raise RuntimeError("PatchTiles inputs must be 11x11 (dta_net_forward_tiles), got {}x{}".format(*images.shape[2:]))
+            x = images
+        else:
+            x = H._check_input(images)
         self._prepare(x.shape, [0])
         m = self.nets_mod[0]
         table = _lib.ScoreTable()
@@ -2087,8 +2098,9 @@ class Predictor:
             table[0][2] = self.logits.data_ptr()
             joint = None
         alpha = _lib.ptr(m.alpha) if m._net_code == _lib.NET_HANG2020 else None
-        _lib.check(L.dta_net_forward(C.byref(self._desc()), self.nets, alpha, _lib.ptr(x), _lib.ptr(self.ws),
-                                     C.byref(table), joint, st), "dta_net_forward")
+        fwd = L.dta_net_forward if tiles is None else L.dta_net_forward_tiles
+        _lib.check(fwd(C.byref(self._desc()), self.nets, alpha, _lib.ptr(x if tiles is None else tiles), _lib.ptr(self.ws),
+                       C.byref(table), joint, st), "dta_net_forward" if tiles is None else "dta_net_forward_tiles")
         self._packed = True
         return self.logits
 

@@ -595,6 +595,38 @@ int dta_meta_head_backward(int batch, int classes, int sites, int training, cons
                            const float* drop, void* workspace, const float* out, const float* dout, const dta_meta_grads* grads,
                            float* dscores, void* stream);
 
+/* ---- Dense per-pixel window prediction over a raster (reference src/patches.py:50-83 `bounds_to_pixel`: one 11x11 window
+ * per pixel of a crown box, read with boundless=True; src/main.py:165-178).  The preprocessing above is per pixel position
+ * and a size x size window resized to size x size is the identity, so the preprocessed window equals the window of the
+ * preprocessed raster, bit for bit (an out-of-bounds pixel, zero-filled by the reference's reader, stays zero).
+ *
+ * dta_raster_normalise: the clipped per-pixel min-max of dta_preprocess_crops (same float32 rounding, same `tiny` rule,
+ * NaNs passed over) for a whole band-first raster raw[bands_raw][height][width] of element type `dtype` (DTA_CROP_*), once.
+ *  tiles == 0: out = float32 [C][height][width], C = dta_preprocess_out_bands(bands_raw, clip)
+ *  tiles != 0: out = bf16 channel chunks [ceil(C / 16)][height * width][16], rounded as dta_preprocess_crops_tiles rounds,
+ *              bands past C zero. */
+int dta_raster_normalise(const void* raw, int bands_raw, int height, int width, int clip, int dtype, int tiles, void* out,
+                         void* stream);
+/* n windows of size x size (4..253, what the networks take) out of the float32 raster [bands][height][width]:
+ * origins [n][2] int32 = (row, col) of each window's top-left corner in raster pixels, device memory; negative origins and
+ * windows that run past the raster are allowed, positions outside the raster are zero.  out: float32 [n][bands][size][size]
+ * (16-byte aligned). */
+int dta_gather_windows(const float* raster, int bands, int height, int width, const int* origins, int n, int size,
+                       float* out, void* stream);
+/* The same out of the bf16 chunk form, written as the tiles dta_net_forward_tiles takes:
+ * tiles bf16 [n][ceil(bands / 16)][size * size][16].  raster and tiles 16-byte aligned. */
+int dta_gather_windows_tiles(const void* raster, int bands, int height, int width, const int* origins, int n, int size,
+                             void* tiles, void* stream);
+/* Per-crown mean of per-window probability rows (reference src/main.py:165-205: the pixel crops of a crown).  Rows arrive
+ * grouped by crown: crown k owns rows offsets[k] .. offsets[k + 1] - 1 of probs [rows][classes] (offsets: int64
+ * [n_crowns + 1], non-decreasing, device memory).  Each class is summed in row order in float32 and divided by the count
+ * (no atomics: reruns are bit-identical).  mean [n_crowns][classes]; top_idx [n_crowns][2] int64 / top_score [n_crowns][2]
+ * = the two largest entries of the mean, ties to the lower class as dta_softmax_top2; count [n_crowns] int32.  An empty
+ * crown: count 0, labels -1, scores and mean 0.  The offsets live on the device, so this call does NOT check them: that
+ * they are non-decreasing and end within the rows of probs is the caller's to guarantee (dense.crown_reduce does). */
+int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns, int classes, float* mean,
+                     long long* top_idx, float* top_score, int* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
