@@ -6,7 +6,8 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.engine     fused train step (forward + weighted CE + backward + Adam, optional RCCL DDP)
     deeptreeattention_amd.hierarchy  <->  src/models/multi_stage.py:368-485 (the levels' predictions -> one species label)
     deeptreeattention_amd.dense      <->  src/patches.py:50-83 + src/main.py:165-205: per-pixel windows of a resident raster,
-                                     gathered and predicted on the device, reduced per crown
+                                     gathered and predicted on the device, reduced per crown; with a multi-stage model
+                                     one species label per pixel and per crown
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.
@@ -16,6 +17,8 @@ from .Hang2020 import set_default_precision, get_default_precision  # noqa: F401
 from .hierarchy import Hierarchy, scores_from_confusion  # noqa: F401
 from .loop import validate, validate_multistage  # noqa: F401
 from .dense import DenseRaster, window_origins, predict_windows, predict_map  # noqa: F401
+from .dense import predict_windows_multistage, predict_map_multistage, crown_resolve  # noqa: F401
 
 __all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
-           "validate", "validate_multistage", "DenseRaster", "window_origins", "predict_windows", "predict_map"]
+           "validate", "validate_multistage", "DenseRaster", "window_origins", "predict_windows", "predict_map",
+           "predict_windows_multistage", "predict_map_multistage", "crown_resolve"]

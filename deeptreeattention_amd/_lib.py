@@ -274,6 +274,12 @@ def lib():
         L.dta_gather_windows_tiles.argtypes = L.dta_gather_windows.argtypes
         L.dta_crown_reduce.restype = C.c_int
         L.dta_crown_reduce.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        L.dta_gather_windows_years.restype = C.c_int
+        L.dta_gather_windows_years.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                               C.POINTER(C.c_void_p), vp, vp, vp]
+        L.dta_crown_resolve.restype = C.c_int
+        L.dta_crown_resolve.argtypes = [C.c_int, C.POINTER(C.c_void_p), vp, C.c_int, C.POINTER(HierarchyTable), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, vp, vp, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["conv.hip", "conv_bf16.hip", "stage.hip", "heads.hip", "capi.hip", "capi_modules.hip", "preprocess.hip", "xchg.hip", "meta.hip", "dense.hip"]
-HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "dta_hip.h")]
+HEADERS = ["common.h", "kernels.h", "walk_dev.h", os.path.join("..", "..", "include", "dta_hip.h")]
 LIB = os.path.join(HERE, "libdta_hip.so")
 # the developer library: the same sources with -DDTA_DEV_SWITCHES (common.h: dev_getenv) -- environment switches for
 # same-box A/B runs of alternative launch plans.  The product library above contains no getenv at all.

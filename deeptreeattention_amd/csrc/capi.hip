@@ -1622,6 +1622,48 @@ int dta_gather_windows_tiles(const void* raster, int bands, int height, int widt
   return launch_gather_windows_tiles(a, (hipStream_t)stream);
 }
 
+int dta_gather_windows_years(const float* const* rasters, int years, int bands, int height, int width, const int* origins,
+                             int n, int size, float* const* outs, float* flags, float* clear_next, void* stream) {
+  const char* who = "dta_gather_windows_years";
+  if (!rasters || !outs || !flags || flags == clear_next) { dta_set_error("%s: null argument (or flags == clear_next)", who); return 1; }
+  if (years < 1 || years > DTA_MAX_YEARS) { dta_set_error("%s: 1..%d years, not %d", who, DTA_MAX_YEARS, years); return 1; }
+  static_assert(DTA_MAX_YEARS <= MAXG, "header and kernel disagree");
+  GatherYearsArgs a;
+  memset(&a, 0, sizeof(a));
+  int present = 0;
+  for (int y = 0; y < years; ++y) {
+    if (!rasters[y]) continue;
+    GatherArgs g;
+    if (gather_args(who, rasters[y], bands, height, width, origins, n, size, outs[y], &g)) return 1;
+    a.g = g; a.rasters[y] = rasters[y]; a.outs[y] = outs[y];
+    ++present;
+  }
+  if (!present) { dta_set_error("%s: every year is missing: nothing to gather", who); return 1; }
+  a.g.raster = nullptr; a.g.out = nullptr;
+  a.years = years; a.flags = flags; a.clear_next = clear_next;
+  return launch_gather_windows_years(a, (hipStream_t)stream);
+}
+
+int dta_crown_resolve(int levels, const float* const* probs, const long long* offsets, int n_crowns,
+                      const dta_hierarchy* table, float* const* mean, long long* const* top_idx, float* const* top_score,
+                      int* count, long long* ens_label, float* ens_score, int* ens_level, const long long* window_labels,
+                      int* votes, void* stream) {
+  const char* who = "dta_crown_resolve";
+  CrownResolveArgs a;
+  memset(&a, 0, sizeof(a));
+  if (!probs || !offsets || !top_idx || !top_score || !count) { dta_set_error("%s: null argument", who); return 1; }
+  if (n_crowns < 1) { dta_set_error("%s: bad shape: crowns=%d", who, n_crowns); return 1; }
+  if ((window_labels != nullptr) != (votes != nullptr)) { dta_set_error("%s: window_labels and votes come together or not at all", who); return 1; }
+  if (hierarchy_args(who, levels, table, ens_label, ens_score, ens_level, nullptr, nullptr, &a.e)) return 1;
+  for (int l = 0; l < levels; ++l) {
+    if (!probs[l] || !top_idx[l] || !top_score[l]) { dta_set_error("%s: level %d: null probabilities or top-2 arrays", who, l); return 1; }
+    a.lv[l].probs = probs[l]; a.lv[l].mean = mean ? mean[l] : nullptr; a.lv[l].top_idx = top_idx[l]; a.lv[l].top_score = top_score[l];
+    a.lv[l].classes = table->classes[l];
+  }
+  a.n = levels; a.n_crowns = n_crowns; a.offsets = offsets; a.count = count; a.win_label = window_labels; a.votes = votes;
+  return launch_crown_resolve(a, (hipStream_t)stream);
+}
+
 int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns, int classes, float* mean,
                      long long* top_idx, float* top_score, int* count, void* stream) {
   if (!probs || !offsets || !mean || !top_idx || !top_score || !count) { dta_set_error("dta_crown_reduce: null argument"); return 1; }

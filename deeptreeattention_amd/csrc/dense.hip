@@ -5,9 +5,13 @@
 //   k_raster_normalise  the raw raster once -> the resident normalised raster (float32 planes, or bf16 channel chunks)
 //   k_gather_windows    N window origins -> the float32 NCHW batch / the first conv's bf16 tiles (pure copies, zero fill)
 //   k_crown_reduce      per-window softmax rows, grouped by crown -> mean vector, its top-2 and the window count
-// All three are bandwidth-bound copies or short reductions: no atomics, fixed summation order, bit-identical reruns.
+// and for a multi-stage model (levels x years networks on the same windows, engine.MultiStagePredictor):
+//   k_gather_windows_years  one batch of windows out of every year's raster in ONE launch, with the years' 0/1 flags
+//   k_crown_resolve         every level's per-crown mean and top-2, the hierarchy walk on them and the crown's window votes
+// All are bandwidth-bound copies or short reductions: no float atomics, fixed summation order, bit-identical reruns.
 #include "../../include/dta_hip.h"
 #include "kernels.h"
+#include "walk_dev.h"
 
 // k_raster_normalise repeats k_preprocess_crops' arithmetic (preprocess.hip) through the same mul_rounded / to_f
 // (common.h): the multiply and the add of the scaling are rounded SEPARATELY, as NumPy's `X *= scale; X += min` does
@@ -65,11 +69,12 @@ __global__ __launch_bounds__(256) void k_raster_normalise(RasterArgs a) {
 // float32 NCHW batch [N][C][S][S] out of the float32 raster [C][H][W].  The batch is one flat array; a lane owns four
 // consecutive elements of it (one 16-byte store; a window's C*S*S floats are not a multiple of four, so a lane's four
 // may straddle rows, planes or windows: the index is decomposed once and carried).  Positions outside the raster: 0.
-__global__ __launch_bounds__(256) void k_gather_windows(GatherArgs a) {
-  const size_t q4 = (size_t)blockIdx.x * 256 + threadIdx.x;
+// (ONE definition for k_gather_windows and k_gather_windows_years: the same lane writes the same bytes in both.)
+// Returns whether any of the lane's elements is non-zero (NaN counts as non-zero).
+__device__ __forceinline__ bool gather_lane(const GatherArgs& a, size_t q4) {
   const size_t total = (size_t)a.N * a.C * a.S * a.S;
   size_t e = q4 * 4;
-  if (e >= total) return;
+  if (e >= total) return false;
   const int S = a.S, SS = S * S;
   const size_t per = (size_t)a.C * SS;
   int n = (int)(e / per);
@@ -101,6 +106,27 @@ __global__ __launch_bounds__(256) void k_gather_windows(GatherArgs a) {
   float* out = reinterpret_cast<float*>(a.out);
   if (e + 4 <= total) *reinterpret_cast<f32x4*>(out + e) = f32x4{v[0], v[1], v[2], v[3]};
   else for (int k = 0; e + k < total; ++k) out[e + k] = v[k];
+  return !(v[0] == 0.f && v[1] == 0.f && v[2] == 0.f && v[3] == 0.f);
+}
+__global__ __launch_bounds__(256) void k_gather_windows(GatherArgs a) {
+  gather_lane(a, (size_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// The same batch of windows out of every year's raster of an ensemble: blockIdx.y = year, every year the lanes and bytes of
+// k_gather_windows.  A year without a raster (NULL) writes nothing: its batch is the caller's persistent zero buffer.
+// flags[y] = 1 when year y's batch has a non-zero element (NaN counts), else it stays 0 -- what k_year_flags (heads.hip)
+// says after reading the finished batch back, here from the values on their way out: a wave that wrote a non-zero element
+// stores 1.f once (plain stores of one value: no atomics, any order).  flags arrive zeroed; clear_next is the bank the
+// NEXT call sets (dta_year_flags' protocol).
+__global__ __launch_bounds__(256) void k_gather_windows_years(GatherYearsArgs a) {
+  const int y = blockIdx.y;
+  if (a.clear_next && blockIdx.x == 0 && threadIdx.x == 0) a.clear_next[y] = 0.f;
+  if (!a.rasters[y]) return;
+  GatherArgs g = a.g;
+  g.raster = a.rasters[y]; g.out = a.outs[y];
+  const bool hit = gather_lane(g, (size_t)blockIdx.x * 256 + threadIdx.x);
+  const bool any = __any(hit);
+  if (any && (threadIdx.x & 63) == 0) a.flags[y] = 1.f;
 }
 
 // The first conv's bf16 tiles [N][NC][S*S][16] (preprocess.PatchTiles) out of the bf16 raster [NC][P][16]: an element
@@ -183,6 +209,85 @@ __global__ __launch_bounds__(256) void k_crown_reduce(CrownArgs a) {
   }
 }
 
+// Every level's k_crown_reduce, the walk on the levels' top-1 (k_hierarchy_resolve) and the crown's window votes in ONE
+// launch: workgroup = crown, wave = level (as k_softmax_top2_ensemble: the levels' top-1 of a crown meet in LDS behind one
+// barrier, where the first eight lanes walk the table).  A lane owns classes lane, lane + 64, ... of its level: the same
+// single float32 accumulator over the crown's rows in row order and the same division as k_crown_reduce, so the mean is
+// that kernel's bit for bit; the top-2 is the two largest under (value descending, class ascending), which does not depend
+// on how the classes are dealt to lanes.  votes: the workgroup zeroes its own row, then counts its windows' labels into it
+// with integer adds (order-independent).
+__global__ __launch_bounds__(64 * BLEND_CE_MULTI_MAX) void k_crown_resolve(CrownResolveArgs a) {
+  __shared__ int s_cls[BLEND_CE_MULTI_MAX];
+  __shared__ float s_score[BLEND_CE_MULTI_MAX];
+  const int lane = threadIdx.x & 63, lvl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), k = blockIdx.x;
+  const long long r0 = a.offsets[k], r1 = a.offsets[k + 1];
+  const long long cnt = r1 > r0 ? r1 - r0 : 0;
+  if (a.votes) {
+    int* row = a.votes + (size_t)k * a.e.n_species;
+    for (int s = threadIdx.x; s < a.e.n_species; s += blockDim.x) row[s] = 0;
+    __threadfence();                                  // the zeros are in place before any wave of this workgroup adds
+  }
+  {
+    const CrownLevel& L = a.lv[lvl];
+    const int classes = L.classes;
+    float* mean = L.mean ? L.mean + (size_t)k * classes : nullptr;
+    const float fc = (float)cnt;
+    float b1 = -1.f, b2 = -1.f;
+    int i1 = -1, i2 = -1;
+    for (int c = lane; c < classes; c += 64) {
+      float mv = 0.f;
+      if (cnt > 0) {
+        const float* src = L.probs + (size_t)r0 * classes + c;
+        float acc = 0.f;
+        long long r = 0;
+        for (; r + 4 <= cnt; r += 4) {      // four loads in flight, added in row order
+          const float v0 = src[(size_t)r * classes], v1 = src[(size_t)(r + 1) * classes];
+          const float v2 = src[(size_t)(r + 2) * classes], v3 = src[(size_t)(r + 3) * classes];
+          acc += v0; acc += v1; acc += v2; acc += v3;
+        }
+        for (; r < cnt; ++r) acc += src[(size_t)r * classes];
+        mv = acc / fc;
+        if (mv > b1) { b2 = b1; i2 = i1; b1 = mv; i1 = c; }
+        else if (mv > b2) { b2 = mv; i2 = c; }
+      }
+      if (mean) mean[c] = mv;               // an empty crown: mean 0, labels -1, scores 0
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
+      const int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
+      auto better = [](float a_, int ia, float b_, int ib) { return ia >= 0 && (ib < 0 || a_ > b_ || (a_ == b_ && ia < ib)); };
+      float n1, n2; int j1, j2;
+      if (better(b1, i1, ob1, oi1)) {
+        n1 = b1; j1 = i1;
+        if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
+      } else {
+        n1 = ob1; j1 = oi1;
+        if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
+      }
+      b1 = n1; i1 = j1; b2 = n2; i2 = j2;
+    }
+    const float t1 = i1 < 0 ? 0.f : b1, t2 = i2 < 0 ? 0.f : b2;
+    if (lane == 0) {
+      L.top_idx[2 * (size_t)k] = i1; L.top_idx[2 * (size_t)k + 1] = i2;
+      L.top_score[2 * (size_t)k] = t1; L.top_score[2 * (size_t)k + 1] = t2;
+      s_cls[lvl] = i1; s_score[lvl] = t1;
+    }
+  }
+  __syncthreads();
+  if (a.votes) {
+    int* row = a.votes + (size_t)k * a.e.n_species;
+    for (long long r = threadIdx.x; r < cnt; r += blockDim.x) {
+      const long long s = a.win_label[r0 + r];
+      if (s >= 0 && s < a.e.n_species) atomicAdd(row + s, 1);
+    }
+  }
+  if (threadIdx.x >= 64) return;
+  if (lane == 0) a.count[k] = (int)cnt;
+  const bool mine = lane < a.n;
+  hierarchy_walk(a.e, a.n, k, lane < 8, lane, mine ? s_cls[lane & 7] : -1, mine ? s_score[lane & 7] : 0.f);
+}
+
 template <typename T>
 int launch_normalise_t(const RasterArgs& a, hipStream_t st) {
   const long long blocks = (a.P + 255) / 256;
@@ -214,6 +319,18 @@ int launch_gather_windows(const GatherArgs& a, hipStream_t st) {
   return 0;
 }
 
+int launch_gather_windows_years(const GatherYearsArgs& a, hipStream_t st) {
+  const size_t total = (size_t)a.g.N * a.g.C * a.g.S * a.g.S, lanes = (total + 3) / 4;
+  const size_t blocks = (lanes + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_windows_years: batch too large for one launch"); return 1; }
+  if (a.years < 1 || a.years > MAXG) { dta_set_error("dta_gather_windows_years: 1..%d years", MAXG); return 1; }
+  // flags must be zero on entry: cleared here, unless the caller alternates two banks and lets each call clear the other
+  if (!a.clear_next && hipMemsetAsync(a.flags, 0, sizeof(float) * a.years, st) != hipSuccess) { dta_set_error("dta_gather_windows_years: memset failed"); return 1; }
+  hipLaunchKernelGGL(k_gather_windows_years, dim3((unsigned)blocks, a.years), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_gather_windows_years");
+  return 0;
+}
+
 int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st) {
   const size_t total = (size_t)a.N * ((a.C + 15) / 16) * a.S * a.S * 2;
   const size_t blocks = (total + 255) / 256;
@@ -226,6 +343,13 @@ int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st) {
 int launch_crown_reduce(const CrownArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_crown_reduce, dim3(a.n_crowns), dim3(256), 1024 * 4, st, a);
   DTA_CHECK_LAUNCH("k_crown_reduce");
+  return 0;
+}
+
+int launch_crown_resolve(const CrownResolveArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > BLEND_CE_MULTI_MAX) { dta_set_error("dta_crown_resolve: 1..%d levels", BLEND_CE_MULTI_MAX); return 1; }
+  hipLaunchKernelGGL(k_crown_resolve, dim3(a.n_crowns), dim3(64 * a.n), 0, st, a);
+  DTA_CHECK_LAUNCH("k_crown_resolve");
   return 0;
 }
 

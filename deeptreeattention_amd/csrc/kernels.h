@@ -689,5 +689,16 @@ int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st);    // bf16
 struct CrownArgs { const float* probs; const long long* offsets; int n_crowns, classes;
                    float* mean; long long* top_idx; float* top_score; int* count; };
 int launch_crown_reduce(const CrownArgs& a, hipStream_t st);
+// the same batch of windows (g: origins, N, C, H, W, S) out of every year's float32 raster (NULL: a missing year, nothing
+// written) into that year's batch, with the years' 0/1 flags (k_year_flags' meaning and bank protocol)
+struct GatherYearsArgs { const float* rasters[MAXG]; float* outs[MAXG]; GatherArgs g; int years; float* flags; float* clear_next; };
+int launch_gather_windows_years(const GatherYearsArgs& a, hipStream_t st);
+// every level's per-crown mean (may be NULL) / top-2 as k_crown_reduce, the crowns' count, the walk on the levels' top-1
+// (e: table and ens_* outputs per crown; e.labels / e.confusion unused) and -- win_label / votes both or neither -- the
+// number of a crown's windows whose own label is each species: votes int32 [n_crowns][e.n_species]
+struct CrownLevel { const float* probs; float* mean; long long* top_idx; float* top_score; int classes; };
+struct CrownResolveArgs { CrownLevel lv[BLEND_CE_MULTI_MAX]; int n, n_crowns; const long long* offsets; int* count;
+                          const long long* win_label; int* votes; HierarchyArgs e; };
+int launch_crown_resolve(const CrownResolveArgs& a, hipStream_t st);
 
 }  // namespace dta

@@ -14,7 +14,23 @@ scikit-learn's "constant" threshold).  Hence:
                          with crown offsets also the per-crown mean, top-2 and count (dta_crown_reduce)
     predict_map          a label map and a score map of a raster region
 
-`gather_windows_np` and `crown_reduce_np` are the written-down meaning of the gather and reduce kernels.
+For a multi-stage model (engine.MultiStagePredictor: levels x years networks on the same windows, then the hierarchy walk):
+
+    DenseRaster.windows_years    one batch of windows out of every year's raster in ONE launch, with the years' 0/1 flags
+                                 taken from the values on their way out (dta_gather_windows_years)
+    predict_windows_multistage   gather -> MultiStagePredictor.ensemble(year_flags=...) per batch: a species label, its score
+                                 and the deciding level per window; with crown offsets also per crown (crown_resolve)
+    predict_map_multistage       a species map, a score map and a level map of a raster region
+    crown_resolve                every level's per-crown mean and top-2, the walk on them, the crown's window votes
+                                 (dta_crown_resolve)
+
+The species of a crown with several windows is THIS package's definition: per level the mean over the crown's windows
+(crown_reduce_np), then the walk over the levels' top-1 of those means (Hierarchy.resolve_np).  The reference has none: its
+`gather_predictions` (multi_stage.py:368-402) takes a flat argmax over one row per individual.  With one window per crown
+the definition is the reference's, exactly.
+
+`gather_windows_np`, `crown_reduce_np` and `crown_resolve_np` are the written-down meaning of the gather, reduce and
+resolve kernels.
 File reading and georeferencing stay with the caller, as in preprocess.py."""
 import collections
 
@@ -90,6 +106,31 @@ def crown_reduce_np(probs, offsets):
         top_idx[k, :len(order)] = order
         top_score[k, :len(order)] = m[order]
     return mean, top_idx, top_score, count
+
+
+CrownSpecies = collections.namedtuple("CrownSpecies", "label score level count top_idx top_score mean votes")
+
+
+def crown_resolve_np(probs_levels, offsets, hierarchy, window_labels=None):
+    """What dta_crown_resolve computes: crown_reduce_np per level, Hierarchy.resolve_np on the levels' top-1 columns, and
+    (window_labels: the windows' own species labels [rows]) the number of each crown's windows per species -- labels
+    outside [0, n_species) are not counted.  Returns CrownSpecies(label int64 [n], score float32 [n], level int32 [n],
+    count int32 [n], top_idx / top_score / mean: one array per level, votes int32 [n][n_species] or None)."""
+    if len(probs_levels) != hierarchy.levels:
+        raise ValueError("the hierarchy has {} levels: one probability array per level".format(hierarchy.levels))
+    offsets = np.asarray(offsets, dtype=np.int64)
+    per = [crown_reduce_np(p, offsets) for p in probs_levels]
+    label, score, level = hierarchy.resolve_np([r[1][:, 0] for r in per], [r[2][:, 0] for r in per])
+    votes = None
+    if window_labels is not None:
+        w = np.asarray(window_labels).astype(np.int64).reshape(-1)
+        n, ns = len(offsets) - 1, hierarchy.n_species
+        votes = np.zeros((n, ns), dtype=np.int32)
+        for k in range(n):
+            mine = w[int(offsets[k]):max(int(offsets[k + 1]), int(offsets[k]))]
+            mine = mine[(mine >= 0) & (mine < ns)]
+            votes[k] = np.bincount(mine, minlength=ns)
+    return CrownSpecies(label, score, level, per[0][3], [r[1] for r in per], [r[2] for r in per], [r[0] for r in per], votes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -175,6 +216,51 @@ class DenseRaster:
         return out
 
 
+    @staticmethod
+    def windows_years(rasters, origins, outs, flags, clear_next, size=WINDOW):
+        """DenseRaster.windows for every year of an ensemble in ONE launch (dta_gather_windows_years).  rasters: one fp32
+        DenseRaster per year (same shape), None for a missing year; outs: one contiguous float32 (N, bands, size, size)
+        tensor per year -- a missing year's is not written (keep it zero); flags / clear_next: two float32 [years] device
+        tensors used alternately by successive calls (dta_year_flags' banks: `flags` zero on entry, `clear_next` zeroed by
+        this call).  flags ends as dta_year_flags' verdict on the years' batches.  Returns flags."""
+        rs = list(rasters)
+        have = _check_years(rs)
+        r0 = have[0]
+        if len(outs) != len(rs):
+            raise ValueError("one output batch per year")
+        o = r0._origins(origins)
+        N, Y = o.shape[0], len(rs)
+        shape = (N, r0.bands, size, size)
+        for t in outs:
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != r0.device:
+                raise ValueError("every year's out must be a contiguous float32 tensor of shape {} on {}".format(shape, r0.device))
+        for t in (flags, clear_next):
+            if t.dtype != torch.float32 or t.numel() != Y or not t.is_contiguous() or t.device != r0.device:
+                raise ValueError("flags and clear_next must be float32 [{}] tensors on {}".format(Y, r0.device))
+        L = _lib.lib()
+        rp = (_lib.C.c_void_p * Y)(*[None if r is None else r.data.data_ptr() for r in rs])
+        op = (_lib.C.c_void_p * Y)(*[t.data_ptr() for t in outs])
+        _lib.check(L.dta_gather_windows_years(rp, Y, r0.bands, r0.height, r0.width, _lib.ptr(o), N, size, op, _lib.ptr(flags),
+                                              _lib.ptr(clear_next), _lib.current_stream_ptr()), "dta_gather_windows_years")
+        return flags
+
+
+def _check_years(rs):
+    """The years' rasters of a multi-stage / float32 ensemble route: fp32 DenseRasters of one shape, None = missing, at
+    least one present.  Returns the present ones.  Launches nothing."""
+    have = [r for r in rs if r is not None]
+    if not have:
+        raise ValueError("at least one year's raster must be present")
+    for r in have:
+        if not isinstance(r, DenseRaster):
+            raise TypeError("rasters must be DenseRaster objects")
+        if r.precision != "fp32":
+            raise RuntimeError("the multi-stage route reads DenseRaster(..., precision='fp32') (bf16 tiles are not taken)")
+        if r.shape != have[0].shape or r.device != have[0].device:
+            raise ValueError("all years' rasters must share one shape and device")
+    return have
+
+
 CrownPredictions = collections.namedtuple("CrownPredictions", "mean top_idx top_score count")
 WindowPredictions = collections.namedtuple("WindowPredictions", "top_idx top_score probs crowns")
 
@@ -199,6 +285,53 @@ def crown_reduce(probs, crown_offsets):
     _lib.check(L.dta_crown_reduce(_lib.ptr(probs), _lib.ptr(off), n, classes, _lib.ptr(out.mean), _lib.ptr(out.top_idx),
                                   _lib.ptr(out.top_score), _lib.ptr(out.count), _lib.current_stream_ptr()), "dta_crown_reduce")
     return out
+
+
+def _host_offsets(crown_offsets, rows):
+    host = crown_offsets.detach().cpu().numpy() if isinstance(crown_offsets, torch.Tensor) else np.asarray(crown_offsets)
+    host = host.astype(np.int64)
+    if host.ndim != 1 or len(host) < 2 or host[0] < 0 or (np.diff(host) < 0).any() or host[-1] > rows:
+        raise ValueError("crown_offsets must be non-decreasing, start at >= 0 and end within the {} rows".format(rows))
+    return np.ascontiguousarray(host)
+
+
+def crown_resolve(probs_levels, crown_offsets, hierarchy, window_labels=None, want_mean=True):
+    """dta_crown_resolve: probs_levels = the levels' device probabilities [rows][classes_l] (float32, contiguous),
+    hierarchy a hierarchy.Hierarchy over those levels, window_labels (int64 [rows] on the device, e.g. the windows'
+    ens_label) for the votes.  Returns CrownSpecies as crown_resolve_np does, on the device (top_idx int64; mean is None
+    with want_mean=False; votes None without window_labels).  The offsets are checked here, before the launch."""
+    probs_levels = list(probs_levels)
+    nl = len(probs_levels)
+    if nl != hierarchy.levels:
+        raise ValueError("the hierarchy has {} levels: one probability tensor per level".format(hierarchy.levels))
+    dev, rows = probs_levels[0].device, probs_levels[0].shape[0]
+    for l, p in enumerate(probs_levels):
+        if (p.dtype != torch.float32 or p.dim() != 2 or not p.is_contiguous() or p.device != dev
+                or tuple(p.shape) != (rows, hierarchy.classes[l])):
+            raise ValueError("level {}: probs must be a contiguous float32 [{}][{}] tensor on {}".format(l, rows, hierarchy.classes[l], dev))
+    if window_labels is not None:
+        w = window_labels
+        if w.dtype != torch.int64 or tuple(w.shape) != (rows,) or not w.is_contiguous() or w.device != dev:
+            raise ValueError("window_labels must be a contiguous int64 [{}] tensor on {}".format(rows, dev))
+    host = _host_offsets(crown_offsets, rows)
+    off, n = torch.from_numpy(host).to(dev), len(host) - 1
+    L = _lib.lib()
+    mean = [torch.empty(n, c, dtype=torch.float32, device=dev) for c in hierarchy.classes] if want_mean else None
+    top_idx = [torch.empty(n, 2, dtype=torch.int64, device=dev) for _ in range(nl)]
+    top_score = [torch.empty(n, 2, dtype=torch.float32, device=dev) for _ in range(nl)]
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    label = torch.empty(n, dtype=torch.int64, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    level = torch.empty(n, dtype=torch.int32, device=dev)
+    votes = torch.empty(n, hierarchy.n_species, dtype=torch.int32, device=dev) if window_labels is not None else None
+    arr = _lib.C.c_void_p * nl
+    table = hierarchy.c_table(dev)
+    _lib.check(L.dta_crown_resolve(nl, arr(*[p.data_ptr() for p in probs_levels]), _lib.ptr(off), n, _lib.C.byref(table),
+                                   arr(*[t.data_ptr() for t in mean]) if want_mean else None,
+                                   arr(*[t.data_ptr() for t in top_idx]), arr(*[t.data_ptr() for t in top_score]),
+                                   _lib.ptr(count), _lib.ptr(label), _lib.ptr(score), _lib.ptr(level),
+                                   _lib.ptr(window_labels), _lib.ptr(votes), _lib.current_stream_ptr()), "dta_crown_resolve")
+    return CrownSpecies(label, score, level, count, top_idx, top_score, mean, votes)
 
 
 def _predictor(model_or_predictor):
@@ -297,3 +430,103 @@ def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=Non
     res = predict_windows(pred, rs, origins, batch_size=batch_size)
     h, w = r1 - r0, c1 - c0
     return res.top_idx[:, 0].reshape(h, w), res.top_score[:, 0].reshape(h, w)
+
+
+MultiStageWindowPredictions = collections.namedtuple("MultiStageWindowPredictions",
+                                                     "ens_label ens_score ens_level top_idx top_score probs crowns")
+
+
+def _multistage_years(predictor, rasters):
+    """The checks of the multi-stage route that need no device: raises before anything is launched.  Returns the years'
+    rasters as a list."""
+    from .engine import MultiStagePredictor
+    if not isinstance(predictor, MultiStagePredictor):
+        raise TypeError("the multi-stage route needs an engine.MultiStagePredictor")
+    rs = list(rasters)
+    years = len(predictor.preds[0].nets_mod)
+    if len(rs) != years:
+        raise ValueError("the levels have {} years: {} rasters are needed (None for a missing year), not {}".format(years, years, len(rs)))
+    if predictor.hierarchy is None:
+        raise RuntimeError("the multi-stage route needs a hierarchy (MultiStagePredictor(models, hierarchy=...))")
+    if not predictor.supported(years):
+        raise RuntimeError("{} levels x {} years are more networks than one chain takes ({}): this route runs one chain only"
+                           .format(len(predictor.preds), years, _lib.MAX_YEARS))
+    if predictor.hierarchy.levels != len(predictor.preds):
+        raise ValueError("the hierarchy has {} levels, the predictor {}".format(predictor.hierarchy.levels, len(predictor.preds)))
+    return rs
+
+
+def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False):
+    """Per-window species prediction of a multi-stage model on 11x11 windows: walks `origins` in batches of `batch_size` --
+    ONE gather launch for all years (dta_gather_windows_years, which also decides the years' flags), then the levels x years
+    forward, every level's softmax / top-2 and the hierarchy walk as MultiStagePredictor.ensemble(year_flags=...) runs them
+    -- copying each batch's outputs into preallocated [N] device tensors; nothing inside the loop waits for the device.
+    predictor: an engine.MultiStagePredictor with a hierarchy whose levels x years fit one chain (predictor.supported).
+    rasters: one DenseRaster(..., precision="fp32") per year, None for a missing year (left out of every level's mean, as
+    is a present year whose batch is all zero: reference year.py:27-33).
+    crown_offsets ([n + 1], windows grouped by crown as window_origins returns them): also one species per crown
+    (crown_resolve: per level the mean over the crown's windows, then the walk -- this package's definition, see the
+    module text) with the crown's window votes.
+    Returns MultiStageWindowPredictions(ens_label int64 [N], ens_score float32 [N], ens_level int32 [N], top_idx / top_score:
+    one [N, 2] tensor per level, probs: one [N, classes_l] tensor per level or None, crowns: CrownSpecies or None)."""
+    rs = _multistage_years(predictor, rasters)
+    have = _check_years(rs)
+    r0 = have[0]
+    dev, size, Y = r0.device, WINDOW, len(rs)
+    o = r0._origins(origins)
+    N = o.shape[0]
+    if crown_offsets is not None:
+        crown_offsets = _host_offsets(crown_offsets, N)
+    classes = [p.nets_mod[0]._classes for p in predictor.preds]
+    nl = len(classes)
+    keep = return_probs or crown_offsets is not None
+    ens = (torch.empty(N, dtype=torch.int64, device=dev), torch.empty(N, dtype=torch.float32, device=dev),
+           torch.empty(N, dtype=torch.int32, device=dev))
+    top_idx = [torch.empty(N, 2, dtype=torch.int64, device=dev) for _ in range(nl)]
+    top_score = [torch.empty(N, 2, dtype=torch.float32, device=dev) for _ in range(nl)]
+    probs = [torch.empty(N, c, dtype=torch.float32, device=dev) for c in classes] if keep else None
+    B = min(int(batch_size), N)
+    if B < 1:
+        raise ValueError("batch_size must be positive")
+    zeros = None
+    if len(have) < Y:      # ONE persistent zero batch stands in for every missing year
+        zeros = torch.zeros(B, r0.bands, size, size, dtype=torch.float32, device=dev)
+    bufs = [zeros if r is None else torch.empty(B, r0.bands, size, size, dtype=torch.float32, device=dev) for r in rs]
+    banks = [torch.zeros(Y, dtype=torch.float32, device=dev) for _ in range(2)]
+    bank = 0
+    for n0 in range(0, N, B):
+        n = min(B, N - n0)
+        xs = [b[:n] for b in bufs]
+        flags = DenseRaster.windows_years(rs, o[n0:n0 + n], xs, banks[bank], banks[bank ^ 1], size=size)
+        bank ^= 1
+        e = predictor.ensemble(xs, year_flags=flags, return_probs=keep)
+        for dst, src in zip(ens, e):
+            dst[n0:n0 + n].copy_(src)
+        for l in range(nl):
+            top_idx[l][n0:n0 + n].copy_(predictor.top_idx[l])
+            top_score[l][n0:n0 + n].copy_(predictor.top_score[l])
+            if keep:
+                probs[l][n0:n0 + n].copy_(predictor.probs[l])
+    crowns = None
+    if crown_offsets is not None:
+        crowns = crown_resolve(probs, crown_offsets, predictor.hierarchy, window_labels=ens[0])
+    return MultiStageWindowPredictions(ens[0], ens[1], ens[2], top_idx, top_score, probs if return_probs else None, crowns)
+
+
+def predict_map_multistage(predictor, rasters, anchor="center", rows=None, cols=None, clip=10, batch_size=4096):
+    """A species map of a raster region from a multi-stage model: rows / cols are half-open (start, stop) pixel ranges
+    (default: the whole raster).  rasters: per year a raw band-first array or a DenseRaster(..., precision="fp32"), None for
+    a missing year.  Returns (species [h][w] int64, score [h][w] float32, level [h][w] int32): each pixel's window's
+    ens_label, the top-1 probability of the level that decided, and that level."""
+    rs = _multistage_years(predictor, rasters)
+    if all(r is None for r in rs):
+        raise ValueError("at least one year's raster must be present")
+    rs = [r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision="fp32", device=predictor.device)
+          for r in rs]
+    first = _check_years(rs)[0]
+    r0, r1 = rows if rows is not None else (0, first.height)
+    c0, c1 = cols if cols is not None else (0, first.width)
+    origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
+    res = predict_windows_multistage(predictor, rs, origins, batch_size=batch_size)
+    h, w = r1 - r0, c1 - c0
+    return res.ens_label.reshape(h, w), res.ens_score.reshape(h, w), res.ens_level.reshape(h, w)

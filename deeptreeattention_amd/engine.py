@@ -2188,17 +2188,20 @@ class MultiStagePredictor:
         self._bank = 0
         self._key = key
 
-    def __call__(self, images, return_probs=True, present=None):
-        """Returns one (probs or None, top_idx [B,2], top_score [B,2]) triple per level; buffers are reused across calls."""
-        return self._run(images, return_probs, present, None)
+    def __call__(self, images, return_probs=True, present=None, year_flags=None):
+        """Returns one (probs or None, top_idx [B,2], top_score [B,2]) triple per level; buffers are reused across calls.
+        year_flags (float32 [years] on the device, instead of `present`): the years' 0/1 flags as dta_year_flags would set
+        them for these images, already known to the caller (dense.predict_windows_multistage: dta_gather_windows_years sets
+        them while it writes the batch) -- used as the gate as they are, and dta_year_flags is not launched."""
+        return self._run(images, return_probs, present, None, year_flags)
 
-    def ensemble(self, images, present=None, labels=None, return_probs=True):
+    def ensemble(self, images, present=None, labels=None, return_probs=True, year_flags=None):
         """The same chain with the hierarchy walk in its last launch (reference multi_stage.py:368-434, `gather_predictions`
         + `ensemble`): returns (ens_label int64 [B], ens_score float32 [B], ens_level int32 [B]) -- the species, the top-1
         probability of the level that decided, and that level; buffers are reused across calls.  labels (int64 [B], species
         labels): the call also counts into `self.confusion` (rows = label, columns = prediction; zero it to start a new
         epoch).  The call's per-level outputs are in self.probs / self.top_idx / self.top_score as after __call__
-        (`per_level()` hands them back as __call__'s triples)."""
+        (`per_level()` hands them back as __call__'s triples).  year_flags: as __call__'s."""
         if self.hierarchy is None:
             raise RuntimeError("MultiStagePredictor.ensemble needs a hierarchy (MultiStagePredictor(models, hierarchy=...))")
         if self.hierarchy.levels != len(self.preds):
@@ -2207,18 +2210,24 @@ class MultiStagePredictor:
             labels = _species_labels(labels, self.device)
             if self.confusion is None:
                 self.confusion = torch.zeros(self.hierarchy.n_species, self.hierarchy.n_species, dtype=torch.int64, device=self.device)
-        self._run(images, return_probs, present, (labels,))
+        self._run(images, return_probs, present, (labels,), year_flags)
         return self._ens
 
     def per_level(self, return_probs=True):
         """The last call's (probs or None, top_idx, top_score) triple per level."""
         return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(len(self.preds))]
 
-    def _run(self, images, return_probs, present, ens):
+    def _run(self, images, return_probs, present, ens, year_flags=None):
         L = _lib.lib()
         st = _lib.current_stream_ptr()
         nl = len(self.preds)
         Y = len(images)
+        if year_flags is not None:
+            if present is not None:
+                raise ValueError("pass `present` (host booleans) or `year_flags` (device flags), not both")
+            if (not isinstance(year_flags, torch.Tensor) or year_flags.dtype != torch.float32 or tuple(year_flags.shape) != (Y,)
+                    or year_flags.device != self.device):
+                raise ValueError("year_flags must be a float32 [{}] tensor on {}".format(Y, self.device))
         if present is None:
             kept = list(range(Y))
         else:
@@ -2231,7 +2240,9 @@ class MultiStagePredictor:
         self._prepare(xs[0].shape, kept)
         xptr = (C.c_void_p * (nl * len(kept)))(*([x.data_ptr() for x in xs] * nl))      # every level reads the same crops
         gate = None
-        if present is None:
+        if year_flags is not None:
+            gate = year_flags.repeat(nl)
+        elif present is None:
             yptr = (C.c_void_p * Y)(*[x.data_ptr() for x in xs])
             flags, nxt = self._banks[self._bank], self._banks[self._bank ^ 1]
             self._bank ^= 1

@@ -627,6 +627,38 @@ int dta_gather_windows_tiles(const void* raster, int bands, int height, int widt
 int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns, int classes, float* mean,
                      long long* top_idx, float* top_score, int* count, void* stream);
 
+
+/* ---- Dense multi-stage prediction: the levels x years networks of a multi-stage model on the windows of the years'
+ * rasters (dta_multistage_predict_ensemble on gathered batches), and ONE species label per crown.
+ *
+ * dta_gather_windows_years: dta_gather_windows for every year of an ensemble in ONE launch.  rasters / outs: HOST arrays of
+ * `years` (1..DTA_MAX_YEARS) device pointers, every raster float32 [bands][height][width], every out float32
+ * [n][bands][size][size]; origins and size are shared.  A NULL raster is a missing year: nothing is written for it (the
+ * caller points that year's network input at a zero buffer of its own) and its flag stays 0; at least one year must be
+ * present.  For a present year the bytes written are dta_gather_windows'.
+ * flags [years] float32 ends as what dta_year_flags says about the years' batches: 1 where a year's batch has a non-zero
+ * element (NaN counts), else 0 -- taken from the values while they are written, so no batch is read back.  Bank protocol
+ * of dta_year_flags: flags must be zero on entry; with clear_next (the other bank, [years]) the call zeroes that bank for
+ * the next call, with clear_next == NULL the call clears flags itself first.  Plain stores only: no atomics. */
+int dta_gather_windows_years(const float* const* rasters, int years, int bands, int height, int width, const int* origins,
+                             int n, int size, float* const* outs, float* flags, float* clear_next, void* stream);
+/* One species per crown out of per-window, per-level probabilities, in ONE launch: for every level what dta_crown_reduce
+ * gives on probs[l] [rows][table->classes[l]] (mean[l] [n_crowns][classes_l] -- `mean` or single entries may be NULL --,
+ * top_idx[l] / top_score[l] [n_crowns][2], bit for bit; count [n_crowns] once), then what dta_hierarchy_resolve gives on
+ * those per-level top-1 columns: ens_label int64 / ens_score / ens_level int32 [n_crowns].  The meaning of a crown with
+ * several windows is THIS library's: the mean over the crown's windows per level, then the walk (the reference has one row
+ * per crown at this point; for one window per crown the two agree exactly).  An empty crown: count 0, per-level labels -1,
+ * ens_label -1, ens_level 0, ens_score 0.
+ * probs / mean / top_idx / top_score: HOST arrays of `levels` device pointers.  window_labels (device int64 [rows], the
+ * windows' own ens_label) and votes (device int32 [n_crowns][n_species]) come together or not at all: votes[k][s] = the
+ * number of crown k's windows whose label is s (labels outside [0, n_species) are not counted); every row is zeroed by the
+ * workgroup that owns it, then counted with integer adds.  No floating-point atomics: reruns are bit-identical.
+ * As for dta_crown_reduce the offsets live on the device and are NOT checked here (dense.crown_resolve does). */
+int dta_crown_resolve(int levels, const float* const* probs, const long long* offsets, int n_crowns,
+                      const dta_hierarchy* table, float* const* mean, long long* const* top_idx, float* const* top_score,
+                      int* count, long long* ens_label, float* ens_score, int* ens_level, const long long* window_labels,
+                      int* votes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

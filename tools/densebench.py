@@ -16,6 +16,16 @@ to end -- host work included, the raw raster in host memory at the start, the la
 legs alternating.  The legs' labels are compared.  The gather launch is also timed alone (events around 20 back-to-back
 launches of one batch) and reported as achieved bytes/s: bytes = 32 read + 32 written per (window, chunk, pixel).
 --only B runs leg B alone (for a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/densebench.py --only B).
+
+    python tools/densebench.py --multistage [--levels 2,2,3,3,3] [--years 3] [--missing 1] [--boxes 64] [--box-side 20] ...
+
+A multi-stage model (levels x years bf16 spectral networks, a chain hierarchy) over the windows of `boxes` crown boxes:
+  leg A : calls the parent commit has: per-year dta_gather_windows into MultiStagePredictor.ensemble(present=None) (which
+          launches dta_year_flags), the same device copies, then per-level dense.crown_reduce + engine.resolve_hierarchy;
+  leg B : dense.predict_windows_multistage (dta_gather_windows_years, ensemble(year_flags=...), dta_crown_resolve).
+Both legs start from resident rasters and share one MultiStagePredictor warmed before the timed region; timed as above.
+Window and crown labels of the legs are compared.  One batch is also timed in pieces (20 back-to-back repeats between
+events): gather + flags each way, and the forward + epilogue chain with and without its own dta_year_flags launch.
 Prints one JSON line."""
 import argparse
 import json
@@ -30,6 +40,161 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _timed(fn, reps=20):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+def multistage(a):
+    import ctypes as C
+    from deeptreeattention_amd import _lib
+    from deeptreeattention_amd.dense import DenseRaster, crown_reduce, predict_windows_multistage, window_origins
+    from deeptreeattention_amd.engine import MultiStagePredictor, resolve_hierarchy
+    from deeptreeattention_amd.hierarchy import Hierarchy
+    from deeptreeattention_amd.year import learned_ensemble
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    S = 11
+    classes = [int(c) for c in a.levels.split(",")]
+    nl, Y = len(classes), a.years
+    # a chain: class 1 of every level but the last passes on to the next level, every other class is a species
+    nxt, sp, ns = [], [], 0
+    for l, c in enumerate(classes):
+        nx = [l + 1 if (k == 1 and l < nl - 1) else -1 for k in range(c)]
+        row = []
+        for v in nx:
+            row.append(ns if v == -1 else -1)
+            ns += v == -1
+        nxt.append(nx)
+        sp.append(row)
+    h = Hierarchy(nxt, sp, ns)
+    torch.manual_seed(3)
+    models = [learned_ensemble(Y, c, {"pretrain_state_dict": None, "bands": a.bands - 20}).to(dev).eval() for c in classes]
+    for m in models:
+        for net in m.year_models:
+            net.precision = "bf16"
+    rng = np.random.default_rng(7)
+    raws = [None if y == a.missing else rng.integers(-500, 9000, size=(a.bands, a.side, a.side), dtype=np.int16) for y in range(Y)]
+    rs = [None if r is None else DenseRaster(r, precision="fp32", device=dev) for r in raws]
+    r0 = next(r for r in rs if r is not None)
+    bs = a.box_side
+    corners = rng.integers(-bs // 2, a.side - bs // 2, size=(a.boxes, 2))
+    boxes = [(int(r), int(c), int(r) + int(rng.integers(1, bs + 1)), int(c) + int(rng.integers(1, bs + 1))) for r, c in corners]
+    origins, offsets = window_origins(boxes, anchor="corner")
+    N = len(origins)
+    o = torch.from_numpy(origins).to(dev)
+    B = min(a.batch, N)
+    pred = MultiStagePredictor(models, frozen=True, hierarchy=h)
+    if not pred.supported(Y):
+        raise SystemExit("levels x years must fit one chain ({} networks)".format(_lib.MAX_YEARS))
+    bufs = [torch.zeros(B, r0.bands, S, S, device=dev) for _ in range(Y)]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pred.ensemble([b for b in bufs], return_probs=True)
+    torch.cuda.synchronize()
+    setup_ms = (time.perf_counter() - t0) * 1e3
+
+    def leg_a():
+        ens = (torch.empty(N, dtype=torch.int64, device=dev), torch.empty(N, dtype=torch.float32, device=dev),
+               torch.empty(N, dtype=torch.int32, device=dev))
+        ti = [torch.empty(N, 2, dtype=torch.int64, device=dev) for _ in range(nl)]
+        ts = [torch.empty(N, 2, dtype=torch.float32, device=dev) for _ in range(nl)]
+        pr = [torch.empty(N, c, dtype=torch.float32, device=dev) for c in classes]
+        for n0 in range(0, N, B):
+            n = min(B, N - n0)
+            xs = [b[:n] if r is None else r.windows(o[n0:n0 + n], out=b[:n]) for r, b in zip(rs, bufs)]
+            e = pred.ensemble(xs, present=None)
+            for d, s_ in zip(ens, e):
+                d[n0:n0 + n].copy_(s_)
+            for l in range(nl):
+                ti[l][n0:n0 + n].copy_(pred.top_idx[l])
+                ts[l][n0:n0 + n].copy_(pred.top_score[l])
+                pr[l][n0:n0 + n].copy_(pred.probs[l])
+        per = [crown_reduce(p, offsets) for p in pr]
+        crown = resolve_hierarchy(h, [c.top_idx for c in per], [c.top_score for c in per])
+        return ens[0], crown[0], crown[1]
+
+    def leg_b():
+        res = predict_windows_multistage(pred, rs, o, crown_offsets=offsets, batch_size=B)
+        return res.ens_label, res.crowns.label, res.crowns.score
+
+    legs = {"A": leg_a, "B": leg_b}
+    if a.only:
+        legs = {k: legs[k] for k in a.only.split(",")}
+    ms, wall, last = {k: [] for k in legs}, {k: [] for k in legs}, {}
+    for rep in range(a.warmup + a.repeats):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            last[k] = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                ms[k].append(e0.elapsed_time(e1))
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+    out = {"tool": "densebench --multistage", "build": L.dta_build_id().decode(), "side": a.side, "bands_raw": a.bands,
+           "levels": classes, "years": Y, "missing_year": a.missing, "boxes": a.boxes, "windows": N, "batch": B,
+           "repeats": a.repeats, "warmup": a.warmup, "predictor_setup_ms": round(setup_ms, 2), "legs": {}}
+    for k in legs:
+        out["legs"][k] = {"event_ms": [round(v, 2) for v in ms[k]], "median_ms": round(statistics.median(ms[k]), 2),
+                          "min_ms": round(min(ms[k]), 2), "max_ms": round(max(ms[k]), 2),
+                          "wall_median_ms": round(statistics.median(wall[k]), 2)}
+    if len(last) == 2:
+        A, Bv = last["A"], last["B"]
+        out["window_labels_identical"] = bool(torch.equal(A[0], Bv[0]))
+        out["crown_labels_identical"] = bool(torch.equal(A[1], Bv[1]))
+        out["crown_score_bits_identical"] = bool(torch.equal(A[2].view(torch.int32), Bv[2].view(torch.int32)))
+        la, lb = out["legs"]["A"], out["legs"]["B"]
+        out["A_spread_ms"] = round(la["max_ms"] - la["min_ms"], 2)
+        out["B_spread_ms"] = round(lb["max_ms"] - lb["min_ms"], 2)
+        out["B_below_A_median_by_more_than_both_spreads"] = bool(lb["median_ms"] < la["median_ms"] - max(out["A_spread_ms"], out["B_spread_ms"]))
+        out["speedup_A_over_B"] = round(la["median_ms"] / lb["median_ms"], 3)
+    # one batch in pieces
+    ob = o[:B]
+    xs = [b[:B] for b in bufs]
+    st = _lib.current_stream_ptr()
+    banks = [torch.zeros(Y, device=dev) for _ in range(2)]
+    ybanks = [torch.zeros(Y, device=dev) for _ in range(2)]
+    xptr = (C.c_void_p * Y)(*[x.data_ptr() for x in xs])
+    state = {"b": 0, "y": 0}
+
+    def gather_a():
+        for r, b in zip(rs, xs):
+            if r is not None:
+                r.windows(ob, out=b)
+        f, nx = ybanks[state["y"]], ybanks[state["y"] ^ 1]
+        state["y"] ^= 1
+        _lib.check(L.dta_year_flags(xptr, Y, xs[0].numel(), _lib.ptr(f), _lib.ptr(nx), st), "dta_year_flags")
+
+    def gather_b():
+        f, nx = banks[state["b"]], banks[state["b"] ^ 1]
+        state["b"] ^= 1
+        state["flags"] = DenseRaster.windows_years(rs, ob, xs, f, nx)
+
+    out["per_batch_us"] = {"windows": B,
+                           "A_gathers_plus_year_flags": round(_timed(gather_a), 1),
+                           "B_gather_windows_years": round(_timed(gather_b), 1)}
+    flags = state["flags"].clone()
+    out["per_batch_us"]["forward_chain_with_own_year_flags"] = round(_timed(lambda: pred.ensemble(xs, present=None)), 1)
+    out["per_batch_us"]["forward_chain_given_year_flags"] = round(_timed(lambda: pred.ensemble(xs, year_flags=flags)), 1)
+    out["per_batch_us"]["year_flags"] = [float(v) for v in flags.cpu().tolist()]
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=256)
@@ -40,9 +205,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--only", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--multistage", action="store_true")
+    ap.add_argument("--levels", default="2,2,3,3,3")
+    ap.add_argument("--years", type=int, default=3)
+    ap.add_argument("--missing", type=int, default=1)
+    ap.add_argument("--boxes", type=int, default=64)
+    ap.add_argument("--box-side", type=int, default=20)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("densebench needs the GPU (no fallback)")
+    if a.multistage:
+        return multistage(a)
     from deeptreeattention_amd import Hang2020 as H
     from deeptreeattention_amd import _lib
     from deeptreeattention_amd.dense import DenseRaster, predict_windows, window_origins
