@@ -9,7 +9,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["conv.hip", "conv_bf16.hip", "stage.hip", "heads.hip", "capi.hip", "capi_modules.hip", "preprocess.hip", "xchg.hip", "meta.hip", "dense.hip"]
-HEADERS = ["common.h", "kernels.h", "walk_dev.h", os.path.join("..", "..", "include", "dta_hip.h")]
+# every header of csrc/ and the public one, taken from the directory: a new header cannot be forgotten (an unlisted one
+# triggers no rebuild when edited and stays out of dta_build_id)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "dta_hip.h")]
 LIB = os.path.join(HERE, "libdta_hip.so")
 # the developer library: the same sources with -DDTA_DEV_SWITCHES (common.h: dev_getenv) -- environment switches for
 # same-box A/B runs of alternative launch plans.  The product library above contains no getenv at all.

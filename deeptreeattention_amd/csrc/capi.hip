@@ -403,6 +403,21 @@ bool add_conv_tab_job(const Plan& p, void* ws, const ConvArgs& geom, int G, int 
 // the loss of a single-score network, taken in the same call as its forward (dta_net_forward_loss)
 struct LossArgs { const long long* labels; const float* weight; float* loss; float* dlogits; float* scratch; };
 
+// What a call adds to the plain forward / backward: an entry point names the members it sets, the rest stay off.
+struct FwdOpts {
+  const void* x_tiles = nullptr;   // the network input already as halo-free bf16 conv tiles (dta_preprocess_crops_tiles): no fp32 input at all
+  const float* gate = nullptr;     // device, per group (year ensembles): a year the step skips keeps its running statistics
+  const LossArgs* loss = nullptr;  // the loss in the same call (the fused tail, or the launch dta_net_loss would issue)
+};
+struct BwdOpts {
+  int phases = 3;                  // bit 0: everything but the first conv's weight gradient, bit 1: that gradient
+  const void* x_tiles = nullptr;   // as FwdOpts
+  float* dalpha32 = nullptr;       // data-parallel (torch / RCCL buckets): alpha's fp32 exchange slot
+  const float* gate = nullptr;     // device, per group: gate[g] <= 0 -> every gradient of group g is an exact zero (its launches still run)
+  dta_xchg* xchg = nullptr;        // peer exchange whose head bucket rides in the first conv's weight-gradient launch, alpha in alpha_slot
+  long long alpha_slot = -1;
+};
+
 // Does this forward end in the fused tail launch (stage.hip: k_tail_fwd)?  A two-branch Hang2020 on 11x11 patches in
 // training mode whose caller wants the last heads only and lets the workspace hold the branch scores.
 bool tail_plan(const Plan& p, const dta_net_desc* d, float* const (*scores)[3]) {
@@ -416,8 +431,8 @@ bool tail_plan(const Plan& p, const dta_net_desc* d, float* const (*scores)[3]) 
 template <typename T>
 int forward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha,
               const float* const* xs, void* ws, float* const (*scores)[3], float* joint, hipStream_t st,
-              const void* x_tiles = nullptr, const float* gate = nullptr, const LossArgs* loss = nullptr) {
-  // x_tiles: the network input already as halo-free bf16 conv tiles (dta_preprocess_crops_tiles): no fp32 input at all
+              const FwdOpts& o) {
+  const void* x_tiles = o.x_tiles; const float* gate = o.gate; const LossArgs* loss = o.loss;
   if (x_tiles && !(p.esz == 2 && p.x_compact && (p.shared_x || p.G == 1))) {
     dta_set_error("input tiles need the bf16 mode, 11x11-class patches and a single input tensor");
     return 1;
@@ -634,9 +649,8 @@ int forward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* net
 
 template <typename T>
 int conv_wgrad_layer(const Plan& p, const dta_net_desc* d, const dta_subnet_grads* grads, void* ws, int L,
-                     WgradReduceGroup& reduces, hipStream_t st, const void* x_tiles = nullptr,
-                     WgradArgs* defer = nullptr, const WgradArgs* partner = nullptr, dta_xchg* xchg = nullptr,
-                     const double* dalpha = nullptr, long long alpha_slot = -1) {
+                     WgradReduceGroup& reduces, hipStream_t st, const BwdOpts& o, const double* dalpha,
+                     WgradArgs* defer = nullptr, const WgradArgs* partner = nullptr) {
   const int G = p.G, B = p.B, C = CH[L];
   const bool cat = L == 0 && p.shared_x;
   const int Nconv = cat ? 32 * G : C;
@@ -646,7 +660,7 @@ int conv_wgrad_layer(const Plan& p, const dta_net_desc* d, const dta_subnet_grad
   if (!want_w) return 0;
   WgradArgs wa;
   memset(&wa, 0, sizeof(wa));
-  if (L == 0) { wa.x_tl = x_tiles ? x_tiles : at<char>(ws, p.x_tl); wa.x_gs = p.x_tl_gs / p.esz; wa.x_compact = p.x_compact; }
+  if (L == 0) { wa.x_tl = o.x_tiles ? o.x_tiles : at<char>(ws, p.x_tl); wa.x_gs = p.x_tl_gs / p.esz; wa.x_compact = p.x_compact; }
   else { wa.x_tl = at<char>(ws, p.a_tl[L - 1]); wa.x_gs = (size_t)B * p.NCin[L] * p.Rin[L] * 16; wa.x_compact = p.tl_compact; }
   wa.NCx = p.NCin[L];
   wa.dy_tl = at<char>(ws, p.dy_tl[L]);
@@ -659,14 +673,14 @@ int conv_wgrad_layer(const Plan& p, const dta_net_desc* d, const dta_subnet_grad
   else {
     prof_begin(DTA_SITE_CONV_WGRAD + L, st);
     bool done = false;
-    if (xchg && L == 0 && !partner && sizeof(T) == 2) {
+    if (o.xchg && L == 0 && !partner && sizeof(T) == 2) {
       // data-parallel peer exchange: the head bucket's reduce-scatter rides in this launch as side workgroups
       XchgArgs side;
-      if (dta_xchg_side_args(xchg, dalpha, alpha_slot, &side) == 0) {
+      if (dta_xchg_side_args(o.xchg, dalpha, o.alpha_slot, &side) == 0) {
         const int rc = launch_conv_wgrad_bf16_xchg(wa, launchG, side, st);
         if (rc == 1) return 1;
         if (rc == 0) done = true;
-        else dta_xchg_side_cancel(xchg);      // (this plan has no combined kernel: the exchange sums the head itself)
+        else dta_xchg_side_cancel(o.xchg);      // (this plan has no combined kernel: the exchange sums the head itself)
       }
     }
     if (!done && (partner ? launch_conv_wgrad_pair_bf16(wa, *partner, launchG, st) : launch_conv_wgrad<T>(wa, launchG, st))) return 1;
@@ -684,15 +698,13 @@ int conv_wgrad_layer(const Plan& p, const dta_net_desc* d, const dta_subnet_grad
 template <typename T>
 int backward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, void* ws,
                const float* const (*dscores)[3], const float* djoint, const dta_subnet_grads* grads, double* dalpha,
-               int phases, hipStream_t st, const void* x_tiles = nullptr, float* dalpha32 = nullptr,
-               const float* gate = nullptr, dta_xchg* xchg = nullptr, long long alpha_slot = -1) {
-  // gate (device, per group; year ensembles): gate[g] <= 0 -> group g's score gradient is taken as zero, so every
-  // gradient of that group comes out as an exact zero (its launches still run)
+               hipStream_t st, const BwdOpts& o) {
   const int G = p.G, B = p.B;
-  if (!(phases & 1)) {
+  const float* gate = o.gate;
+  if (!(o.phases & 1)) {
     // phase 2 only: the first layer's weight gradient from tensors phase 1 left in the workspace
     WgradReduceGroup reduces;
-    if (conv_wgrad_layer<T>(p, d, grads, ws, 0, reduces, st, x_tiles)) return 1;
+    if (conv_wgrad_layer<T>(p, d, grads, ws, 0, reduces, st, o, dalpha)) return 1;
     return launch_wgrad_reduce_group(reduces, st);
   }
   const float* dsc[MAXG][3] = {};
@@ -740,7 +752,7 @@ int backward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* ne
   WgradReduceGroup reduces;   // likewise the split-K reductions of the conv weight gradients
   // data-parallel (torch / RCCL buckets): alpha's finished float64 gradient is rounded ONCE into its fp32 exchange slot
   // by the launch that ends this call (phase 1 or the whole backward)
-  if (dalpha32 && blend_fin_pending) { reduces.slot_src = dalpha; reduces.slot_dst = dalpha32; }
+  if (o.dalpha32 && blend_fin_pending) { reduces.slot_src = dalpha; reduces.slot_dst = o.dalpha32; }
   for (int L = 2; L >= 0; --L) {
     const int C = CH[L];
     StageArgs sa = stage_args(p, d, nets, ws, L);
@@ -878,23 +890,22 @@ int backward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* ne
       prof_end(DTA_SITE_GEMM + 2, st);
       deferred.n = 0;
     }
-    if (L > 0 || (phases & 2)) {
+    if (L > 0 || (o.phases & 2)) {
       bool want1 = false;
       for (int g = 0; g < G; ++g) want1 |= grads[g].conv_w[1] != nullptr;
       if (L == 2 && p.wgrad_pair && want1) {
-        if (conv_wgrad_layer<T>(p, d, grads, ws, L, reduces, st, x_tiles, &pair_conv3)) return 1;
+        if (conv_wgrad_layer<T>(p, d, grads, ws, L, reduces, st, o, dalpha, &pair_conv3)) return 1;
         bool want3 = false;
         for (int g = 0; g < G; ++g) want3 |= grads[g].conv_w[2] != nullptr;
         pair_pending = want3;
       } else {
-        if (L == 0 && xchg) {
+        if (L == 0 && o.xchg) {
           // the exchange's head bucket (everything but the first conv's weights) must be COMPLETE before the launch whose
           // side workgroups sum it over the ranks: the parameter-gradient GEMMs and the other layers' slab reductions go now
           if (deferred.n > 0 ? launch_gemm_group_with_reduce(deferred, reduces, st, sizeof(T) == 2) : launch_wgrad_reduce_group(reduces, st)) return 1;
           deferred.n = 0; reduces.n = 0;
         }
-        if (conv_wgrad_layer<T>(p, d, grads, ws, L, reduces, st, x_tiles, nullptr, (L == 1 && pair_pending) ? &pair_conv3 : nullptr,
-                                L == 0 ? xchg : nullptr, dalpha, alpha_slot)) return 1;
+        if (conv_wgrad_layer<T>(p, d, grads, ws, L, reduces, st, o, dalpha, nullptr, (L == 1 && pair_pending) ? &pair_conv3 : nullptr)) return 1;
       }
     }
     // ---- conv input gradient (feeds the previous stage's gated map) ----
@@ -918,6 +929,23 @@ int backward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* ne
   }
   if (deferred.n > 0) return launch_gemm_group_with_reduce(deferred, reduces, st, sizeof(T) == 2);
   return launch_wgrad_reduce_group(reduces, st);
+}
+
+// the one dtype switch of the forward and of the backward
+int run_forward(const Plan& p, const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const float* const* xs,
+                void* ws, float* const (*scores)[3], float* joint, hipStream_t st, const FwdOpts& o = {}) {
+  if (d->dtype == DTA_BF16) return forward_t<bf16_t>(p, d, nets, alpha, xs, ws, scores, joint, st, o);
+  if (d->dtype == DTA_F32) return forward_t<float>(p, d, nets, alpha, xs, ws, scores, joint, st, o);
+  dta_set_error("unknown dtype %d", d->dtype);
+  return 1;
+}
+int run_backward(const Plan& p, const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, void* ws,
+                 const float* const (*dscores)[3], const float* djoint, const dta_subnet_grads* grads, double* dalpha,
+                 hipStream_t st, const BwdOpts& o = {}) {
+  if (d->dtype == DTA_BF16) return backward_t<bf16_t>(p, d, nets, alpha, ws, dscores, djoint, grads, dalpha, st, o);
+  if (d->dtype == DTA_F32) return backward_t<float>(p, d, nets, alpha, ws, dscores, djoint, grads, dalpha, st, o);
+  dta_set_error("unknown dtype %d", d->dtype);
+  return 1;
 }
 
 }  // namespace
@@ -999,12 +1027,8 @@ int dta_net_forward(const dta_net_desc* d, const dta_subnet_params* nets, const 
   Plan p;
   if (!d || !nets || !x || !workspace) { dta_set_error("dta_net_forward: null argument"); return 1; }
   if (build_plan(d, &p)) return 1;
-  hipStream_t st = (hipStream_t)stream;
   const float* xs[MAXG] = {x, x, x, x};
-  if (d->dtype == DTA_BF16) return forward_t<bf16_t>(p, d, nets, alpha, xs, workspace, scores, joint, st);
-  if (d->dtype == DTA_F32) return forward_t<float>(p, d, nets, alpha, xs, workspace, scores, joint, st);
-  dta_set_error("unknown dtype %d", d->dtype);
-  return 1;
+  return run_forward(p, d, nets, alpha, xs, workspace, scores, joint, (hipStream_t)stream);
 }
 
 int dta_net_forward_tiles(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const void* x_tiles,
@@ -1014,7 +1038,7 @@ int dta_net_forward_tiles(const dta_net_desc* d, const dta_subnet_params* nets, 
   if (build_plan(d, &p)) return 1;
   if (d->dtype != DTA_BF16) { dta_set_error("dta_net_forward_tiles: bf16 mode only"); return 1; }
   const float* xs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-  return forward_t<bf16_t>(p, d, nets, alpha, xs, workspace, scores, joint, (hipStream_t)stream, x_tiles);
+  return run_forward(p, d, nets, alpha, xs, workspace, scores, joint, (hipStream_t)stream, {.x_tiles = x_tiles});
 }
 
 int dta_net_forward_loss(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const float* x,
@@ -1029,12 +1053,8 @@ int dta_net_forward_loss(const dta_net_desc* d, const dta_subnet_params* nets, c
   dta_net_desc dd = *d;
   if (d->kind == DTA_NET_HANG2020) dd.heads_mask |= DTA_SKIP_BLEND;      // the blend belongs to the loss launch (or the fused tail)
   const LossArgs la = {labels, weight, loss, dlogits, scratch};
-  hipStream_t st = (hipStream_t)stream;
   const float* xs[MAXG] = {x, x, x, x};
-  if (dd.dtype == DTA_BF16) return forward_t<bf16_t>(p, &dd, nets, alpha, xs, workspace, nullptr, joint, st, x_tiles, nullptr, &la);
-  if (dd.dtype == DTA_F32) return forward_t<float>(p, &dd, nets, alpha, xs, workspace, nullptr, joint, st, nullptr, nullptr, &la);
-  dta_set_error("unknown dtype %d", d->dtype);
-  return 1;
+  return run_forward(p, &dd, nets, alpha, xs, workspace, nullptr, joint, (hipStream_t)stream, {.x_tiles = x_tiles, .loss = &la});
 }
 
 int dta_net_backward_tiles(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const void* x_tiles,
@@ -1044,64 +1064,96 @@ int dta_net_backward_tiles(const dta_net_desc* d, const dta_subnet_params* nets,
   if (!d || !nets || !x_tiles || !workspace || !grads || !(phases & 3)) { dta_set_error("dta_net_backward_tiles: null argument"); return 1; }
   if (build_plan(d, &p)) return 1;
   if (d->dtype != DTA_BF16) { dta_set_error("dta_net_backward_tiles: bf16 mode only"); return 1; }
-  return backward_t<bf16_t>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, phases, (hipStream_t)stream, x_tiles);
+  return run_backward(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, (hipStream_t)stream, {.phases = phases, .x_tiles = x_tiles});
 }
 
-// ---- year ensemble: `years` spectral networks as the groups of ONE set of launches ----
-static int ensemble_desc(const dta_net_desc* d, int years, dta_net_desc* out, Plan* p, const char* who) {
+// ---- grouped calls: several spectral networks -- the years of an ensemble, the levels x years of a multi-stage step --
+//      as the groups of ONE set of launches.  A forward entry point is: its null checks, ensemble_desc / multistage_desc
+//      and grouped_inputs, the checks particular to it, grouped_forward, then ONE epilogue launch over its levels. ----
+struct Grouped { Plan p; dta_net_desc dd; };
+
+static int ensemble_desc(const char* who, const dta_net_desc* d, int years, Grouped* g) {
   if (!d || years < 1 || years > MAXG) { dta_set_error("%s: 1..%d years", who, MAXG); return 1; }
   if (d->kind != DTA_NET_SPECTRAL) { dta_set_error("%s: the descriptor's kind must be DTA_NET_SPECTRAL", who); return 1; }
-  *out = *d;
-  out->heads_mask = 4 | (d->heads_mask & (DTA_FORWARD_ONLY | DTA_REUSE_PACKED));   // the ensemble keeps each year's last head only (reference year.py:30)
-  return build_plan(out, p, years);
+  g->dd = *d;
+  g->dd.heads_mask = 4 | (d->heads_mask & (DTA_FORWARD_ONLY | DTA_REUSE_PACKED));   // the ensemble keeps each year's last head only (reference year.py:30)
+  return build_plan(&g->dd, &g->p, years);
 }
 
 size_t dta_ensemble_workspace_bytes(const dta_net_desc* d, int years) {
-  Plan p; dta_net_desc dd;
-  if (ensemble_desc(d, years, &dd, &p, "dta_ensemble_workspace_bytes")) return 0;
-  return p.total;
+  Grouped g;
+  return ensemble_desc("dta_ensemble_workspace_bytes", d, years, &g) ? 0 : g.p.total;
+}
+
+// every group's input is there (`unit`: what the caller calls a group)
+static int grouped_inputs(const char* who, const char* unit, const Grouped& g, const float* const* x) {
+  for (int i = 0; i < g.p.G; ++i)
+    if (!x[i]) { dta_set_error("%s: null input for %s %d", who, unit, i); return 1; }
+  return 0;
+}
+// the forward of every group; gate (may be null): a group the step skips keeps its BatchNorm running statistics
+static int grouped_forward(const Grouped& g, const dta_subnet_params* nets, const float* const* x, const float* gate,
+                           void* workspace, hipStream_t st) {
+  return run_forward(g.p, &g.dd, nets, nullptr, x, workspace, nullptr, nullptr, st, {.gate = gate});
+}
+// ... and the backward: `dsc` holds each group's last-head score gradient (dsc_level), nothing else carries one
+static int grouped_backward(const Grouped& g, const dta_subnet_params* nets, void* workspace, const float* const (*dsc)[3],
+                            const dta_subnet_grads* grads, hipStream_t st, const BwdOpts& o) {
+  return run_backward(g.p, &g.dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, st, o);
+}
+// d(mean)/d(year score) is the same for every kept year of a level: all of its groups read the level's one dscore
+static void dsc_level(const float* (*dsc)[3], int first, int count, const float* dscore) {
+  for (int k = 0; k < count; ++k) dsc[first + k][2] = dscore;
+}
+
+// A level is the groups [first, first + count) (dta_level; a year ensemble is the one level [0, years)).  What an epilogue
+// launch reads of it: `src` receives where each group's last head left its scores in the workspace, the level's slice of
+// the gate is returned.
+static const float* level_sources(const Grouped& g, void* workspace, const float* gate, const dta_level& lv, const float** src) {
+  for (int k = 0; k < lv.count; ++k) src[k] = at<float>(workspace, g.p.scores[lv.first + k][2]);
+  return gate ? gate + lv.first : nullptr;
+}
+// the level's mean over its kept years (reference year.py:33) ...
+static MeanArgs level_mean(const Grouped& g, void* workspace, const float* gate, const dta_level& lv) {
+  MeanArgs a = {};
+  a.gate = level_sources(g, workspace, gate, lv, a.src);
+  a.n = lv.count; a.dst = lv.mean_scores; a.count = (size_t)g.p.B * lv.classes; a.kept = lv.kept;
+  return a;
+}
+// ... and its loss over that mean (multi_stage.py:277-288)
+static BlendCeArgs level_ce(const Grouped& g, void* workspace, const float* gate, const dta_level& lv) {
+  BlendCeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.gscale = 1.f;
+  a.src_gate = level_sources(g, workspace, gate, lv, a.src);
+  a.nsrc = lv.count; a.kept_out = lv.kept; a.joint = lv.mean_scores;
+  a.labels = lv.labels; a.weight = lv.weight; a.dlogits = lv.dscore; a.loss = lv.loss; a.rowtmp = lv.scratch;
+  a.B = g.p.B; a.classes = lv.classes;
+  return a;
 }
 
 static int ensemble_forward_impl(const dta_net_desc* d, int years, const dta_subnet_params* nets, const float* const* x,
                                  const float* gate, void* workspace, float* mean_scores, float* kept, void* stream) {
-  Plan p; dta_net_desc dd;
-  if (!nets || !x || !workspace || !mean_scores) { dta_set_error("dta_ensemble_forward: null argument"); return 1; }
-  if (ensemble_desc(d, years, &dd, &p, "dta_ensemble_forward")) return 1;
-  for (int g = 0; g < years; ++g)
-    if (!x[g]) { dta_set_error("dta_ensemble_forward: null input for year %d", g); return 1; }
+  Grouped g;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  if (rc) return rc;
-  MeanArgs ma = {};
-  for (int g = 0; g < years; ++g) ma.src[g] = at<float>(workspace, p.scores[g][2]);
-  ma.n = years; ma.dst = mean_scores; ma.count = (size_t)p.B * p.classes; ma.gate = gate; ma.kept = kept;
-  return launch_mean_scores(ma, st);
+  if (!nets || !x || !workspace || !mean_scores) { dta_set_error("dta_ensemble_forward: null argument"); return 1; }
+  if (ensemble_desc("dta_ensemble_forward", d, years, &g) || grouped_inputs("dta_ensemble_forward", "year", g, x)) return 1;
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
+  const dta_level all = {.classes = g.p.classes, .first = 0, .count = years, .mean_scores = mean_scores, .kept = kept};
+  return launch_mean_scores(level_mean(g, workspace, gate, all), st);
 }
 
 int dta_ensemble_forward_loss(const dta_net_desc* d, int years, const dta_subnet_params* nets, const float* const* x,
                               const float* gate, void* workspace, const long long* labels, const float* weight,
                               float* mean_scores, float* kept, float* loss, float* dscore, float* scratch, void* stream) {
-  Plan p; dta_net_desc dd;
-  if (!nets || !x || !workspace || !labels || !loss || !scratch) { dta_set_error("dta_ensemble_forward_loss: null argument"); return 1; }
-  if (ensemble_desc(d, years, &dd, &p, "dta_ensemble_forward_loss")) return 1;
-  for (int g = 0; g < years; ++g)
-    if (!x[g]) { dta_set_error("dta_ensemble_forward_loss: null input for year %d", g); return 1; }
+  Grouped g;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  if (rc) return rc;
-  BlendCeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.gscale = 1.f;
-  for (int g = 0; g < years; ++g) a.src[g] = at<float>(workspace, p.scores[g][2]);
-  a.nsrc = years; a.src_gate = gate; a.kept_out = kept; a.joint = mean_scores;
-  a.labels = labels; a.weight = weight; a.dlogits = dscore; a.loss = loss; a.rowtmp = scratch; a.B = p.B; a.classes = p.classes;
-  return launch_blend_ce(a, st);
+  if (!nets || !x || !workspace || !labels || !loss || !scratch) { dta_set_error("dta_ensemble_forward_loss: null argument"); return 1; }
+  if (ensemble_desc("dta_ensemble_forward_loss", d, years, &g) || grouped_inputs("dta_ensemble_forward_loss", "year", g, x)) return 1;
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
+  const dta_level all = {.classes = g.p.classes, .first = 0, .count = years, .labels = labels, .weight = weight, .mean_scores = mean_scores,
+                         .kept = kept, .loss = loss, .dscore = dscore, .scratch = scratch};
+  return launch_blend_ce(level_ce(g, workspace, gate, all), st);
 }
 
 int dta_ensemble_forward(const dta_net_desc* d, int years, const dta_subnet_params* nets, const float* const* x,
@@ -1132,39 +1184,32 @@ int dta_ensemble_backward_phased(const dta_net_desc* d, int years, const dta_sub
   return dta_ensemble_backward_gated(d, years, nets, workspace, dscore, grads, nullptr, phases, stream);
 }
 
+static int ensemble_backward_impl(const char* who, const dta_net_desc* d, int years, const dta_subnet_params* nets, void* workspace,
+                                  const float* dscore, const dta_subnet_grads* grads, void* stream, const BwdOpts& o) {
+  Grouped g;
+  if (ensemble_desc(who, d, years, &g)) return 1;
+  const float* dsc[MAXG][3] = {};
+  dsc_level(dsc, 0, years, dscore);
+  return grouped_backward(g, nets, workspace, dsc, grads, (hipStream_t)stream, o);
+}
+
 int dta_ensemble_backward_gated(const dta_net_desc* d, int years, const dta_subnet_params* nets, void* workspace,
                                 const float* dscore, const dta_subnet_grads* grads, const float* gate, int phases,
                                 void* stream) {
-  Plan p; dta_net_desc dd;
   if (!nets || !workspace || !dscore || !grads || !(phases & 3)) { dta_set_error("dta_ensemble_backward: null argument"); return 1; }
-  if (ensemble_desc(d, years, &dd, &p, "dta_ensemble_backward")) return 1;
-  const float* dsc[MAXG][3] = {};
-  for (int g = 0; g < years; ++g) dsc[g][2] = dscore;   // d(mean)/d(year score) is the same 1/years for every year
-  hipStream_t st = (hipStream_t)stream;
-  if (dd.dtype == DTA_BF16) return backward_t<bf16_t>(p, &dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, phases, st, nullptr, nullptr, gate);
-  if (dd.dtype == DTA_F32) return backward_t<float>(p, &dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, phases, st, nullptr, nullptr, gate);
-  dta_set_error("unknown dtype %d", dd.dtype);
-  return 1;
+  return ensemble_backward_impl("dta_ensemble_backward", d, years, nets, workspace, dscore, grads, stream, {.phases = phases, .gate = gate});
 }
 
 int dta_ensemble_backward_xchg(const dta_net_desc* d, int years, const dta_subnet_params* nets, void* workspace,
                                const float* dscore, const dta_subnet_grads* grads, const float* gate, dta_xchg* xchg,
                                void* stream) {
-  Plan p; dta_net_desc dd;
   if (!nets || !workspace || !dscore || !grads || !xchg) { dta_set_error("dta_ensemble_backward_xchg: null argument"); return 1; }
-  if (ensemble_desc(d, years, &dd, &p, "dta_ensemble_backward_xchg")) return 1;
-  const float* dsc[MAXG][3] = {};
-  for (int g = 0; g < years; ++g) dsc[g][2] = dscore;
-  hipStream_t st = (hipStream_t)stream;
-  if (dd.dtype == DTA_BF16) return backward_t<bf16_t>(p, &dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, 3, st, nullptr, nullptr, gate, xchg, -1);
-  if (dd.dtype == DTA_F32) return backward_t<float>(p, &dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, 3, st, nullptr, nullptr, gate, xchg, -1);
-  dta_set_error("unknown dtype %d", dd.dtype);
-  return 1;
+  return ensemble_backward_impl("dta_ensemble_backward_xchg", d, years, nets, workspace, dscore, grads, stream, {.gate = gate, .xchg = xchg});
 }
 
 // ---- multi-stage step: the levels x years networks of the reference's hierarchical model as the groups of ONE set of
 //      launches (reference src/models/multi_stage.py:41-66 one learned_ensemble per level, :277-288 one loss per level) ----
-static int multistage_desc(const dta_net_desc* d, int levels, const dta_level* lv, dta_net_desc* out, Plan* p, const char* who) {
+static int multistage_desc(const char* who, const dta_net_desc* d, int levels, const dta_level* lv, Grouped* g) {
   if (!d || !lv || levels < 1 || levels > DTA_MAX_LEVELS) { dta_set_error("%s: 1..%d levels", who, DTA_MAX_LEVELS); return 1; }
   static_assert(DTA_MAX_LEVELS == BLEND_CE_MULTI_MAX, "header and kernel disagree");
   if (d->kind != DTA_NET_SPECTRAL) { dta_set_error("%s: the descriptor's kind must be DTA_NET_SPECTRAL", who); return 1; }
@@ -1175,96 +1220,77 @@ static int multistage_desc(const dta_net_desc* d, int levels, const dta_level* l
     if (lv[l].classes < 1) { dta_set_error("%s: level %d has %d classes", who, l, lv[l].classes); return 1; }
     for (int k = 0; k < lv[l].count; ++k) cls[G++] = lv[l].classes;
   }
-  *out = *d;
-  out->heads_mask = 4 | (d->heads_mask & (DTA_FORWARD_ONLY | DTA_REUSE_PACKED));   // each year's last head only (reference year.py:30)
-  out->classes = cls[0];
-  return build_plan(out, p, G, cls);
+  g->dd = *d;
+  g->dd.heads_mask = 4 | (d->heads_mask & (DTA_FORWARD_ONLY | DTA_REUSE_PACKED));   // each year's last head only (reference year.py:30)
+  g->dd.classes = cls[0];
+  return build_plan(&g->dd, &g->p, G, cls);
 }
 
 size_t dta_multistage_workspace_bytes(const dta_net_desc* d, int levels, const dta_level* lv) {
-  Plan p; dta_net_desc dd;
-  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_workspace_bytes")) return 0;
-  return p.total;
+  Grouped g;
+  return multistage_desc("dta_multistage_workspace_bytes", d, levels, lv, &g) ? 0 : g.p.total;
+}
+
+static int loss_levels_present(const char* who, int levels, const dta_level* lv) {
+  for (int l = 0; l < levels; ++l)
+    if (!lv[l].labels || !lv[l].loss || !lv[l].scratch) { dta_set_error("%s: level %d: labels, loss and scratch are required", who, l); return 1; }
+  return 0;
+}
+// every level's softmax + top-2 over the mean of its kept years
+static SoftmaxMulti softmax_levels(const Grouped& g, int levels, const dta_level* lv, void* workspace, const float* gate,
+                                   float* const* probs, long long* const* top_idx, float* const* top_score) {
+  SoftmaxMulti m;
+  memset(&m, 0, sizeof(m));
+  m.n = levels; m.B = g.p.B;
+  for (int l = 0; l < levels; ++l) {
+    SoftmaxLevel& a = m.lv[l];
+    a.gate = level_sources(g, workspace, gate, lv[l], a.src);
+    a.nsrc = lv[l].count; a.mean_out = lv[l].mean_scores; a.classes = lv[l].classes;
+    a.probs = probs ? probs[l] : nullptr; a.top_idx = top_idx[l]; a.top_score = top_score[l];
+  }
+  return m;
 }
 
 int dta_multistage_forward_loss(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                                 const float* const* x, const float* gate, void* workspace, void* stream) {
-  Plan p; dta_net_desc dd;
-  if (!nets || !x || !workspace) { dta_set_error("dta_multistage_forward_loss: null argument"); return 1; }
-  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_forward_loss")) return 1;
-  for (int g = 0; g < p.G; ++g)
-    if (!x[g]) { dta_set_error("dta_multistage_forward_loss: null input for network %d", g); return 1; }
-  for (int l = 0; l < levels; ++l)
-    if (!lv[l].labels || !lv[l].loss || !lv[l].scratch) { dta_set_error("dta_multistage_forward_loss: level %d: labels, loss and scratch are required", l); return 1; }
+  const char* who = "dta_multistage_forward_loss";
+  Grouped g;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  if (rc) return rc;
+  if (!nets || !x || !workspace) { dta_set_error("%s: null argument", who); return 1; }
+  if (multistage_desc(who, d, levels, lv, &g) || grouped_inputs(who, "network", g, x) || loss_levels_present(who, levels, lv)) return 1;
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
   BlendCeMulti m;
   memset(&m, 0, sizeof(m));
   m.n = levels;
-  for (int l = 0; l < levels; ++l) {
-    BlendCeArgs& a = m.a[l];
-    a.gscale = 1.f;
-    for (int k = 0; k < lv[l].count; ++k) a.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
-    a.nsrc = lv[l].count; a.src_gate = gate ? gate + lv[l].first : nullptr; a.kept_out = lv[l].kept; a.joint = lv[l].mean_scores;
-    a.labels = lv[l].labels; a.weight = lv[l].weight; a.dlogits = lv[l].dscore; a.loss = lv[l].loss; a.rowtmp = lv[l].scratch;
-    a.B = p.B; a.classes = lv[l].classes;
-  }
+  for (int l = 0; l < levels; ++l) m.a[l] = level_ce(g, workspace, gate, lv[l]);
   return launch_blend_ce_multi(m, st);
 }
 
 int dta_multistage_forward(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                            const float* const* x, const float* gate, void* workspace, void* stream) {
-  Plan p; dta_net_desc dd;
-  if (!nets || !x || !workspace) { dta_set_error("dta_multistage_forward: null argument"); return 1; }
-  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_forward")) return 1;
-  for (int g = 0; g < p.G; ++g)
-    if (!x[g]) { dta_set_error("dta_multistage_forward: null input for network %d", g); return 1; }
-  for (int l = 0; l < levels; ++l)
-    if (!lv[l].mean_scores) { dta_set_error("dta_multistage_forward: level %d has no score output", l); return 1; }
+  const char* who = "dta_multistage_forward";
+  Grouped g;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  if (rc) return rc;
-  for (int l = 0; l < levels; ++l) {      // each level's mean over its kept years (reference year.py:33)
-    MeanArgs ma = {};
-    for (int k = 0; k < lv[l].count; ++k) ma.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
-    ma.n = lv[l].count; ma.dst = lv[l].mean_scores; ma.count = (size_t)p.B * lv[l].classes;
-    ma.gate = gate ? gate + lv[l].first : nullptr; ma.kept = lv[l].kept;
-    if (launch_mean_scores(ma, st)) return 1;
-  }
+  if (!nets || !x || !workspace) { dta_set_error("%s: null argument", who); return 1; }
+  if (multistage_desc(who, d, levels, lv, &g) || grouped_inputs(who, "network", g, x)) return 1;
+  for (int l = 0; l < levels; ++l)
+    if (!lv[l].mean_scores) { dta_set_error("%s: level %d has no score output", who, l); return 1; }
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
+  for (int l = 0; l < levels; ++l)
+    if (launch_mean_scores(level_mean(g, workspace, gate, lv[l]), st)) return 1;
   return 0;
 }
 
 int dta_multistage_predict(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                            const float* const* x, const float* gate, void* workspace, float* const* probs,
                            long long* const* top_idx, float* const* top_score, void* stream) {
-  Plan p; dta_net_desc dd;
-  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("dta_multistage_predict: null argument"); return 1; }
-  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_predict")) return 1;
-  for (int g = 0; g < p.G; ++g)
-    if (!x[g]) { dta_set_error("dta_multistage_predict: null input for network %d", g); return 1; }
+  const char* who = "dta_multistage_predict";
+  Grouped g;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  if (rc) return rc;
-  SoftmaxMulti m;
-  memset(&m, 0, sizeof(m));
-  m.n = levels; m.B = p.B;
-  for (int l = 0; l < levels; ++l) {
-    SoftmaxLevel& a = m.lv[l];
-    for (int k = 0; k < lv[l].count; ++k) a.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
-    a.nsrc = lv[l].count; a.gate = gate ? gate + lv[l].first : nullptr; a.mean_out = lv[l].mean_scores; a.classes = lv[l].classes;
-    a.probs = probs ? probs[l] : nullptr; a.top_idx = top_idx[l]; a.top_score = top_score[l];
-  }
-  return launch_softmax_top2_multi(m, st);
+  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("%s: null argument", who); return 1; }
+  if (multistage_desc(who, d, levels, lv, &g) || grouped_inputs(who, "network", g, x)) return 1;
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
+  return launch_softmax_top2_multi(softmax_levels(g, levels, lv, workspace, gate, probs, top_idx, top_score), st);
 }
 
 // ---- validation: eval-mode forward of every level + ONE epilogue launch (loss, softmax, top-2, metric counts) ----
@@ -1280,36 +1306,25 @@ static int eval_level_args(const char* who, int l, const dta_eval_level* ev, Eva
 int dta_multistage_validate(const dta_net_desc* d, int levels, const dta_level* lv, const dta_eval_level* ev,
                             const dta_subnet_params* nets, const float* const* x, const float* gate,
                             void* workspace, void* stream) {
-  Plan p; dta_net_desc dd;
   const char* who = "dta_multistage_validate";
+  Grouped g;
+  hipStream_t st = (hipStream_t)stream;
   if (!d || !lv || !ev) { dta_set_error("%s: null argument", who); return 1; }
   if (d->training != 0) { dta_set_error("%s: validation runs eval-mode BatchNorm: the descriptor's training must be 0", who); return 1; }
   if (!(d->heads_mask & DTA_FORWARD_ONLY)) { dta_set_error("%s: the descriptor's heads_mask must carry DTA_FORWARD_ONLY", who); return 1; }
   if (d->heads_mask & DTA_REUSE_PACKED) { dta_set_error("%s: DTA_REUSE_PACKED is refused: validation follows weight updates", who); return 1; }
-  if (multistage_desc(d, levels, lv, &dd, &p, who)) return 1;
+  if (multistage_desc(who, d, levels, lv, &g)) return 1;
   EvalMulti m;
   memset(&m, 0, sizeof(m));
   m.n = levels;
   for (int l = 0; l < levels; ++l)
     if (eval_level_args(who, l, ev + l, &m.lv[l])) return 1;
   if (!nets || !x || !workspace) { dta_set_error("%s: null argument", who); return 1; }
-  for (int g = 0; g < p.G; ++g)
-    if (!x[g]) { dta_set_error("%s: null input for network %d", who, g); return 1; }
-  for (int l = 0; l < levels; ++l)
-    if (!lv[l].labels || !lv[l].loss || !lv[l].scratch) { dta_set_error("%s: level %d: labels, loss and scratch are required", who, l); return 1; }
-  if (dd.dtype != DTA_BF16 && dd.dtype != DTA_F32) { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  if (rc) return rc;
+  if (grouped_inputs(who, "network", g, x) || loss_levels_present(who, levels, lv)) return 1;
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
   for (int l = 0; l < levels; ++l) {
-    BlendCeArgs& a = m.lv[l].ce;
-    a.gscale = 1.f;
-    for (int k = 0; k < lv[l].count; ++k) a.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
-    a.nsrc = lv[l].count; a.src_gate = gate ? gate + lv[l].first : nullptr; a.kept_out = lv[l].kept; a.joint = lv[l].mean_scores;
-    a.labels = lv[l].labels; a.weight = lv[l].weight; a.loss = lv[l].loss; a.rowtmp = lv[l].scratch;
-    a.B = p.B; a.classes = lv[l].classes;
+    m.lv[l].ce = level_ce(g, workspace, gate, lv[l]);
+    m.lv[l].ce.dlogits = nullptr;      // the forward part of the loss only
   }
   return launch_eval_metrics_multi(m, st);
 }
@@ -1355,33 +1370,19 @@ int dta_multistage_predict_ensemble(const dta_net_desc* d, int levels, const dta
                                     long long* const* top_idx, float* const* top_score, const dta_hierarchy* table,
                                     long long* ens_label, float* ens_score, int* ens_level, const long long* labels,
                                     long long* confusion, void* stream) {
-  Plan p; dta_net_desc dd; HierarchyArgs e;
-  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("dta_multistage_predict_ensemble: null argument"); return 1; }
-  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_predict_ensemble")) return 1;
-  if (hierarchy_args("dta_multistage_predict_ensemble", levels, table, ens_label, ens_score, ens_level, labels, confusion, &e)) return 1;
+  const char* who = "dta_multistage_predict_ensemble";
+  Grouped g; HierarchyArgs e;
+  hipStream_t st = (hipStream_t)stream;
+  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("%s: null argument", who); return 1; }
+  if (multistage_desc(who, d, levels, lv, &g) || grouped_inputs(who, "network", g, x)) return 1;
+  if (hierarchy_args(who, levels, table, ens_label, ens_score, ens_level, labels, confusion, &e)) return 1;
   for (int l = 0; l < levels; ++l)
     if (lv[l].classes != table->classes[l]) {
-      dta_set_error("dta_multistage_predict_ensemble: level %d has %d classes, the hierarchy table %d", l, lv[l].classes, table->classes[l]);
+      dta_set_error("%s: level %d has %d classes, the hierarchy table %d", who, l, lv[l].classes, table->classes[l]);
       return 1;
     }
-  for (int g = 0; g < p.G; ++g)
-    if (!x[g]) { dta_set_error("dta_multistage_predict_ensemble: null input for network %d", g); return 1; }
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (dd.dtype == DTA_BF16) rc = forward_t<bf16_t>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else if (dd.dtype == DTA_F32) rc = forward_t<float>(p, &dd, nets, nullptr, x, workspace, nullptr, nullptr, st, nullptr, gate);
-  else { dta_set_error("unknown dtype %d", dd.dtype); return 1; }
-  if (rc) return rc;
-  SoftmaxMulti m;
-  memset(&m, 0, sizeof(m));
-  m.n = levels; m.B = p.B;
-  for (int l = 0; l < levels; ++l) {
-    SoftmaxLevel& a = m.lv[l];
-    for (int k = 0; k < lv[l].count; ++k) a.src[k] = at<float>(workspace, p.scores[lv[l].first + k][2]);
-    a.nsrc = lv[l].count; a.gate = gate ? gate + lv[l].first : nullptr; a.mean_out = lv[l].mean_scores; a.classes = lv[l].classes;
-    a.probs = probs ? probs[l] : nullptr; a.top_idx = top_idx[l]; a.top_score = top_score[l];
-  }
-  return launch_softmax_top2_ensemble(m, e, st);
+  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
+  return launch_softmax_top2_ensemble(softmax_levels(g, levels, lv, workspace, gate, probs, top_idx, top_score), e, st);
 }
 
 int dta_hierarchy_resolve(int levels, const long long* const* top_idx, const float* const* top_score, int batch,
@@ -1401,19 +1402,15 @@ int dta_hierarchy_resolve(int levels, const long long* const* top_idx, const flo
 
 int dta_multistage_backward(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                             void* workspace, const dta_subnet_grads* grads, const float* gate, void* stream) {
-  Plan p; dta_net_desc dd;
+  Grouped g;
   if (!nets || !workspace || !grads) { dta_set_error("dta_multistage_backward: null argument"); return 1; }
-  if (multistage_desc(d, levels, lv, &dd, &p, "dta_multistage_backward")) return 1;
+  if (multistage_desc("dta_multistage_backward", d, levels, lv, &g)) return 1;
   const float* dsc[MAXG][3] = {};
   for (int l = 0; l < levels; ++l) {
     if (!lv[l].dscore) { dta_set_error("dta_multistage_backward: level %d has no score gradient", l); return 1; }
-    for (int k = 0; k < lv[l].count; ++k) dsc[lv[l].first + k][2] = lv[l].dscore;   // d(mean)/d(year score) is the same for every kept year
+    dsc_level(dsc, lv[l].first, lv[l].count, lv[l].dscore);
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (dd.dtype == DTA_BF16) return backward_t<bf16_t>(p, &dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, 3, st, nullptr, nullptr, gate);
-  if (dd.dtype == DTA_F32) return backward_t<float>(p, &dd, nets, nullptr, workspace, dsc, nullptr, grads, nullptr, 3, st, nullptr, nullptr, gate);
-  dta_set_error("unknown dtype %d", dd.dtype);
-  return 1;
+  return grouped_backward(g, nets, workspace, dsc, grads, (hipStream_t)stream, {.gate = gate});
 }
 
 int dta_net_backward(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, void* workspace,
@@ -1422,11 +1419,7 @@ int dta_net_backward(const dta_net_desc* d, const dta_subnet_params* nets, const
   Plan p;
   if (!d || !nets || !workspace || !grads || !(phases & 3)) { dta_set_error("dta_net_backward: null argument"); return 1; }
   if (build_plan(d, &p)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == DTA_BF16) return backward_t<bf16_t>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, phases, st);
-  if (d->dtype == DTA_F32) return backward_t<float>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, phases, st);
-  dta_set_error("unknown dtype %d", d->dtype);
-  return 1;
+  return run_backward(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, (hipStream_t)stream, {.phases = phases});
 }
 
 int dta_net_backward_dp(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const void* x_tiles,
@@ -1435,12 +1428,9 @@ int dta_net_backward_dp(const dta_net_desc* d, const dta_subnet_params* nets, co
   Plan p;
   if (!d || !nets || !workspace || !grads || !(phases & 3)) { dta_set_error("dta_net_backward_dp: null argument"); return 1; }
   if (build_plan(d, &p)) return 1;
-  hipStream_t st = (hipStream_t)stream;
   if (x_tiles && d->dtype != DTA_BF16) { dta_set_error("dta_net_backward_dp: tile input is bf16 mode only"); return 1; }
-  if (d->dtype == DTA_BF16) return backward_t<bf16_t>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, phases, st, x_tiles, dalpha_f32);
-  if (d->dtype == DTA_F32) return backward_t<float>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, phases, st, nullptr, dalpha_f32);
-  dta_set_error("unknown dtype %d", d->dtype);
-  return 1;
+  return run_backward(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, (hipStream_t)stream,
+                      {.phases = phases, .x_tiles = x_tiles, .dalpha32 = dalpha_f32});
 }
 
 int dta_net_backward_xchg(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const void* x_tiles,
@@ -1449,12 +1439,9 @@ int dta_net_backward_xchg(const dta_net_desc* d, const dta_subnet_params* nets, 
   Plan p;
   if (!d || !nets || !workspace || !grads || !xchg) { dta_set_error("dta_net_backward_xchg: null argument"); return 1; }
   if (build_plan(d, &p)) return 1;
-  hipStream_t st = (hipStream_t)stream;
   if (x_tiles && d->dtype != DTA_BF16) { dta_set_error("dta_net_backward_xchg: tile input is bf16 mode only"); return 1; }
-  if (d->dtype == DTA_BF16) return backward_t<bf16_t>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, 3, st, x_tiles, nullptr, nullptr, xchg, alpha_slot);
-  if (d->dtype == DTA_F32) return backward_t<float>(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, 3, st, nullptr, nullptr, nullptr, xchg, alpha_slot);
-  dta_set_error("unknown dtype %d", d->dtype);
-  return 1;
+  return run_backward(p, d, nets, alpha, workspace, dscores, djoint, grads, dalpha, (hipStream_t)stream,
+                      {.x_tiles = x_tiles, .xchg = xchg, .alpha_slot = alpha_slot});
 }
 
 int dta_net_loss(const dta_net_desc* d, const double* alpha, void* workspace, const long long* labels, const float* weight,
