@@ -18,6 +18,7 @@ from .hierarchy import Hierarchy, scores_from_confusion  # noqa: F401
 from .loop import validate, validate_multistage  # noqa: F401
 from .dense import DenseRaster, window_origins, predict_windows, predict_map  # noqa: F401
 from .dense import predict_windows_multistage, predict_map_multistage, crown_resolve  # noqa: F401
+from .dense import predict_windows_metadata, predict_map_metadata  # noqa: F401
 
 __all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
            "validate", "validate_multistage", "DenseRaster", "window_origins", "predict_windows", "predict_map",

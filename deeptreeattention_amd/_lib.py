@@ -170,6 +170,13 @@ def lib():
         L.dta_meta_head_backward.restype = C.c_int
         L.dta_meta_head_backward.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MetaParams), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MetaGrads), C.c_void_p, C.c_void_p]
+        L.dta_meta_predict_workspace_bytes.restype = C.c_size_t
+        L.dta_meta_predict_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.dta_meta_site_table.restype = C.c_int
+        L.dta_meta_site_table.argtypes = [C.c_int, C.c_int, C.c_float, C.POINTER(MetaParams), C.c_void_p, C.c_void_p]
+        L.dta_meta_predict.restype = C.c_int
+        L.dta_meta_predict.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dta_net_loss.restype = C.c_int
         L.dta_net_loss.argtypes = [C.POINTER(NetDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -9,6 +9,7 @@
 // and the backward's batch sums are sums over sites of per-site gradient sums.  Everything is evaluated in a fixed order
 // (no float atomics): reruns give the same bits.
 #include <atomic>
+#include <stdint.h>
 #include <string.h>
 
 #include "../../include/dta_hip.h"
@@ -297,6 +298,220 @@ int check(int B, int C, int S, const dta_meta_params* p, const long long* site, 
 }
 int grid1d(size_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
+// ------------------------------------------------------------------------------------------------
+// Prediction.  In eval mode (running statistics, no dropout) the site branch depends on the site alone, so the first
+// `classes` columns of fc1 contribute one bias row per site:
+//   T[s][c]   = fc_b[c] + sum_j fc_w[c][j] * ReLU(mlp_b[j] + sum_f mlp_w[j][f] * bn(E[s][f]))         j < C, f < 16
+//   out[b][c] = ReLU(T[site_b][c] + sum_k fc_w[c][C + k] * hsi[b][k])                                 k < C
+// k_meta_site_table writes T [S][C] and Wh[k][c] = fc_w[c][C + k] (so that the lanes of the fused kernel read consecutive
+// classes) into the caller's workspace; k_meta_fuse_top2 is the whole head + softmax + top-2 of a batch in one launch.
+// Nothing here is a one-workgroup kernel: neither the batch nor the number of sites is capped by LDS.
+// ------------------------------------------------------------------------------------------------
+constexpr int TS = 4, TC = 64;      // k_meta_site_table: a workgroup owns 4 sites x 64 classes (thread = one T[s][c])
+constexpr int PR = 8;               // k_meta_fuse_top2: rows per workgroup
+constexpr int MAX_PRED_CLASSES = 1020;      // two [PR][classes] float tiles + the rows' sites in 64 KB of LDS
+constexpr int MAX_PRED_SITES = 1 << 20;     // (T is global memory: a bound on the grid, not on LDS)
+
+struct PredictPlan { size_t table, wh, total; };
+PredictPlan predict_plan(int C, int S) {
+  PredictPlan p;
+  Carver c;
+  p.table = c.take((size_t)S * C * 4);
+  p.wh = c.take((size_t)C * C * 4);
+  p.total = c.off;
+  return p;
+}
+
+struct TableArgs {
+  const float* emb; const float* bn_w; const float* bn_b; const float* rm; const float* rv;
+  const float* mlp_w; const float* mlp_b; const float* fc_w; const float* fc_b;
+  float* T; float* Wh; int C, S; float eps;
+};
+
+// grid (ceil(S / 4), ceil(C / 64)), 256 threads: thread (site sl = t / 64, class cl = t % 64) owns T[s][c], ONE float32
+// accumulator that starts at fc_b[c] and takes j ascending.  fc_w's rows are 2C floats apart, so a [64 classes][64 j] tile
+// is read along j (coalesced) and handed over through LDS (row stride 65 words: conflict-free both ways).  The same tile
+// buffer transposes the HSI half of fc_w into Wh; the k chunks are dealt out over blockIdx.x.
+__global__ __launch_bounds__(256) void k_meta_site_table(TableArgs a) {
+  __shared__ float x16[TS][MW];        // bn(E[s]) of the workgroup's sites
+  __shared__ float h[TS][TC];          // the site branch's outputs j0 .. j0 + 63 of those sites
+  __shared__ float wt[TC][TC + 1];
+  const int t = threadIdx.x, cl = t & 63, sl = t >> 6;
+  const int C = a.C, S = a.S, s0 = blockIdx.x * TS, c0 = blockIdx.y * TC;
+  const int s = s0 + sl, c = c0 + cl;
+  if (t < TS * MW) {
+    const int ss = s0 + (t >> 4), f = t & (MW - 1);
+    float v = 0.f;
+    if (ss < S) {
+      const float xh = (a.emb[(size_t)ss * MW + f] - a.rm[f]) * rsqrtf(a.rv[f] + a.eps);      // (as k_meta_front's eval branch)
+      v = xh * a.bn_w[f] + a.bn_b[f];
+    }
+    x16[t >> 4][f] = v;
+  }
+  float acc = c < C ? a.fc_b[c] : 0.f;
+  __syncthreads();
+  for (int j0 = 0; j0 < C; j0 += TC) {
+    const int j = j0 + cl;
+    float hv = 0.f;
+    if (j < C) {
+      const float* wr = a.mlp_w + (size_t)j * MW;
+      float m = 0.f;
+#pragma unroll
+      for (int f = 0; f < MW; ++f) m = fmaf(wr[f], x16[sl][f], m);
+      m += a.mlp_b[j];
+      hv = m < 0.f ? 0.f : m;
+    }
+    h[sl][cl] = hv;
+#pragma unroll 4
+    for (int r = sl; r < TC; r += TS) {
+      const int cr = c0 + r;
+      wt[r][cl] = (cr < C && j < C) ? a.fc_w[(size_t)cr * 2 * C + j] : 0.f;
+    }
+    __syncthreads();
+    const int n = min(TC, C - j0);
+#pragma unroll 8
+    for (int jj = 0; jj < n; ++jj) acc = fmaf(wt[cl][jj], h[sl][jj], acc);
+    __syncthreads();
+  }
+  if (s < S && c < C) a.T[(size_t)s * C + c] = acc;
+  for (int k0 = blockIdx.x * TC; k0 < C; k0 += gridDim.x * TC) {
+    const int k = k0 + cl;
+#pragma unroll 4
+    for (int r = sl; r < TC; r += TS) {
+      const int cr = c0 + r;
+      wt[r][cl] = (cr < C && k < C) ? a.fc_w[(size_t)cr * 2 * C + C + k] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int r = sl; r < TC; r += TS)
+      if (k0 + r < C && c < C) a.Wh[(size_t)(k0 + r) * C + c] = wt[cl][r];
+    __syncthreads();
+  }
+}
+
+struct FuseArgs {
+  const float* T; const float* Wh; const long long* site; long long site_all; const float* scores;
+  float* out; float* probs; long long* top_idx; float* top_score; int B, C, S;
+};
+
+// grid ceil(B / 8), 256 threads.  Phase 1: thread = class (c = t, t + 256, ...), eight float32 accumulators (one per row of
+// the tile) that start at T[site][c] and take k ascending: Wh[k][c] comes coalesced out of L2 (independent of the
+// accumulators, so the loads run ahead), the rows' HSI scores are LDS broadcasts of four k at a time.  Phase 2: wave = row
+// (two rows per wave), k_softmax_top2's arithmetic and tie rule on the tile's fused scores in LDS.
+// A row's instructions do not depend on its place in the tile or on the batch size: its bits do not either.
+// dynamic LDS: hs [8][Cp] | sc [8][Cp], Cp = C rounded up to 4
+__global__ __launch_bounds__(256) void k_meta_fuse_top2(FuseArgs a) {
+  extern __shared__ float lds[];
+  __shared__ int srow[PR];             // the rows' sites; -1 = not a row of the batch, or a site outside [0, S)
+  const int C = a.C, Cp = (C + 3) & ~3;
+  float* hs = lds;
+  float* sc = lds + PR * Cp;
+  const int t = threadIdx.x, r0 = blockIdx.x * PR;
+  for (int i = t; i < PR * Cp; i += 256) {
+    const int r = i / Cp, k = i - r * Cp;
+    hs[i] = (r0 + r < a.B && k < C) ? a.scores[(size_t)(r0 + r) * C + k] : 0.f;
+  }
+  if (t < PR) {
+    long long s = -1;
+    if (r0 + t < a.B) s = a.site ? a.site[r0 + t] : a.site_all;
+    srow[t] = (s >= 0 && s < a.S) ? (int)s : -1;      // (tested here, before T is read)
+  }
+  __syncthreads();
+  const int K4 = C & ~3;
+  for (int c = t; c < C; c += 256) {
+    float acc[PR];
+#pragma unroll
+    for (int r = 0; r < PR; ++r) {
+      const int s = srow[r];
+      acc[r] = s >= 0 ? a.T[(size_t)s * C + c] : 0.f;
+    }
+    const float* w = a.Wh + c;
+    int k = 0;
+#pragma unroll 2
+    for (; k < K4; k += 4) {
+      const float w0 = w[(size_t)k * C], w1 = w[(size_t)(k + 1) * C], w2 = w[(size_t)(k + 2) * C], w3 = w[(size_t)(k + 3) * C];
+#pragma unroll
+      for (int r = 0; r < PR; ++r) {
+        const f32x4 hv = *reinterpret_cast<const f32x4*>(hs + r * Cp + k);
+        acc[r] = fmaf(w0, hv[0], acc[r]);
+        acc[r] = fmaf(w1, hv[1], acc[r]);
+        acc[r] = fmaf(w2, hv[2], acc[r]);
+        acc[r] = fmaf(w3, hv[3], acc[r]);
+      }
+    }
+    for (; k < C; ++k) {
+      const float w0 = w[(size_t)k * C];
+#pragma unroll
+      for (int r = 0; r < PR; ++r) acc[r] = fmaf(w0, hs[r * Cp + k], acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < PR; ++r) sc[r * Cp + c] = acc[r] < 0.f ? 0.f : acc[r];      // (a NaN stays a NaN, as torch.relu)
+  }
+  __syncthreads();
+  const int lane = t & 63, wv = t >> 6;
+#pragma unroll
+  for (int q = 0; q < PR / 4; ++q) {
+    const int r = wv + 4 * q, row = r0 + r;
+    if (row >= a.B) continue;
+    if (srow[r] < 0) {
+      // k_crown_reduce's empty-crown convention: labels -1, scores and rows 0
+      for (int n = lane; n < C; n += 64) {
+        if (a.out) a.out[(size_t)row * C + n] = 0.f;
+        if (a.probs) a.probs[(size_t)row * C + n] = 0.f;
+      }
+      if (lane == 0) {
+        a.top_idx[(size_t)row * 2] = -1; a.top_idx[(size_t)row * 2 + 1] = -1;
+        a.top_score[(size_t)row * 2] = 0.f; a.top_score[(size_t)row * 2 + 1] = 0.f;
+      }
+      continue;
+    }
+    const float* z = sc + r * Cp;
+    float mx = -3.4e38f;
+    for (int n = lane; n < C; n += 64) mx = fmaxf(mx, z[n]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int n = lane; n < C; n += 64) se += __expf(z[n] - mx);
+    se = wave_sum(se);
+    const float inv = 1.f / se;
+    float b1 = -1.f, b2 = -1.f;
+    int i1 = -1, i2 = -1;
+    for (int n = lane; n < C; n += 64) {
+      const float zn = z[n], pr = __expf(zn - mx) * inv;
+      if (a.out) a.out[(size_t)row * C + n] = zn;
+      if (a.probs) a.probs[(size_t)row * C + n] = pr;
+      if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = n; }
+      else if (pr > b2) { b2 = pr; i2 = n; }
+    }
+    // the lanes' (best, second) pairs merged across the wave as k_softmax_top2 does: ties go to the lower class
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
+      const int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
+      auto better = [](float x, int ix, float y, int iy) { return x > y || (x == y && ix >= 0 && (iy < 0 || ix < iy)); };
+      float n1, n2; int j1, j2;
+      if (better(b1, i1, ob1, oi1)) {
+        n1 = b1; j1 = i1;
+        if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
+      } else {
+        n1 = ob1; j1 = oi1;
+        if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
+      }
+      b1 = n1; i1 = j1; b2 = n2; i2 = j2;
+    }
+    if (lane == 0) {
+      a.top_idx[(size_t)row * 2] = i1; a.top_idx[(size_t)row * 2 + 1] = i2;
+      a.top_score[(size_t)row * 2] = b1; a.top_score[(size_t)row * 2 + 1] = b2;
+    }
+  }
+}
+
+bool misaligned(const void* p, size_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
+int check_predict_shape(int C, int S, const char* who) {
+  if (C < 2 || C > MAX_PRED_CLASSES || S < 1 || S > MAX_PRED_SITES) {
+    dta_set_error("%s: unsupported shape (2 <= classes <= %d, 1 <= sites <= %d)", who, MAX_PRED_CLASSES, MAX_PRED_SITES); return 1; }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -406,6 +621,54 @@ int dta_meta_head_backward(int batch, int classes, int sites, int training, cons
     dta_set_error("dta_meta_head_backward: the device refused %zu bytes of dynamic LDS", lds_budget()); return 1; }
   hipLaunchKernelGGL(k_meta_back, dim3(1), dim3(1024), lds, st, ba);
   DTA_CHECK_LAUNCH("k_meta_back");
+  return 0;
+}
+
+size_t dta_meta_predict_workspace_bytes(int classes, int sites) {
+  if (check_predict_shape(classes, sites, "dta_meta_predict_workspace_bytes")) return 0;
+  return predict_plan(classes, sites).total;
+}
+
+int dta_meta_site_table(int classes, int sites, float eps, const dta_meta_params* p, void* workspace, void* stream) {
+  const int C = classes, S = sites;
+  if (check_predict_shape(C, S, "dta_meta_site_table")) return 1;
+  if (!p || !workspace) { dta_set_error("dta_meta_site_table: null argument"); return 1; }
+  if (!p->emb || !p->bn_w || !p->bn_b || !p->bn_rm || !p->bn_rv || !p->mlp_w || !p->mlp_b || !p->fc_w || !p->fc_b) {
+    dta_set_error("dta_meta_site_table: null parameter"); return 1; }
+  if (misaligned(workspace, 16)) { dta_set_error("dta_meta_site_table: the workspace must be 16-byte aligned"); return 1; }
+  const float* fp[] = {p->emb, p->bn_w, p->bn_b, p->bn_rm, p->bn_rv, p->mlp_w, p->mlp_b, p->fc_w, p->fc_b};
+  for (const float* q : fp)
+    if (misaligned(q, 4)) { dta_set_error("dta_meta_site_table: a parameter is not 4-byte aligned"); return 1; }
+  if (!(eps >= 0.f)) { dta_set_error("dta_meta_site_table: eps must be >= 0"); return 1; }
+  const PredictPlan pl = predict_plan(C, S);
+  TableArgs a;
+  a.emb = p->emb; a.bn_w = p->bn_w; a.bn_b = p->bn_b; a.rm = p->bn_rm; a.rv = p->bn_rv;
+  a.mlp_w = p->mlp_w; a.mlp_b = p->mlp_b; a.fc_w = p->fc_w; a.fc_b = p->fc_b;
+  a.T = at<float>(workspace, pl.table); a.Wh = at<float>(workspace, pl.wh); a.C = C; a.S = S; a.eps = eps;
+  hipLaunchKernelGGL(k_meta_site_table, dim3((S + TS - 1) / TS, (C + TC - 1) / TC), dim3(256), 0, (hipStream_t)stream, a);
+  DTA_CHECK_LAUNCH("k_meta_site_table");
+  return 0;
+}
+
+int dta_meta_predict(int batch, int classes, int sites, const void* workspace, const long long* site, long long site_all,
+                     const float* scores, float* out, float* probs, long long* top_idx, float* top_score, void* stream) {
+  const int B = batch, C = classes, S = sites;
+  if (check_predict_shape(C, S, "dta_meta_predict")) return 1;
+  if (B < 1) { dta_set_error("dta_meta_predict: batch must be positive"); return 1; }
+  if (!workspace || !scores || !top_idx || !top_score) { dta_set_error("dta_meta_predict: null argument"); return 1; }
+  if (misaligned(workspace, 16) || misaligned(scores, 4) || misaligned(out, 4) || misaligned(probs, 4) || misaligned(top_score, 4) ||
+      misaligned(top_idx, 8) || misaligned(site, 8)) { dta_set_error("dta_meta_predict: misaligned argument"); return 1; }
+  if (!site && (site_all < 0 || site_all >= S)) {
+    dta_set_error("dta_meta_predict: site %lld is outside [0, %d)", site_all, S); return 1; }
+  const PredictPlan pl = predict_plan(C, S);
+  FuseArgs a;
+  a.T = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + pl.table);
+  a.Wh = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + pl.wh);
+  a.site = site; a.site_all = site_all; a.scores = scores; a.out = out; a.probs = probs; a.top_idx = top_idx; a.top_score = top_score;
+  a.B = B; a.C = C; a.S = S;
+  const size_t lds = (size_t)2 * PR * ((C + 3) & ~3) * 4;
+  hipLaunchKernelGGL(k_meta_fuse_top2, dim3((B + PR - 1) / PR), dim3(256), lds, (hipStream_t)stream, a);
+  DTA_CHECK_LAUNCH("k_meta_fuse_top2");
   return 0;
 }
 

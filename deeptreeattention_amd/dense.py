@@ -24,6 +24,12 @@ For a multi-stage model (engine.MultiStagePredictor: levels x years networks on 
     crown_resolve                every level's per-crown mean and top-2, the walk on them, the crown's window votes
                                  (dta_crown_resolve)
 
+For the site-metadata fusion model (engine.MetadataPredictor; every window of a raster shares the raster's site):
+
+    predict_windows_metadata     gather -> the sensor model's eval forward -> the whole head, softmax and top-2 in ONE launch
+                                 per batch (dta_meta_predict with the raster's site); with crown offsets also crown_reduce
+    predict_map_metadata         a label map and a score map of a raster region
+
 The species of a crown with several windows is THIS package's definition: per level the mean over the crown's windows
 (crown_reduce_np), then the walk over the levels' top-1 of those means (Hierarchy.resolve_np).  The reference has none: its
 `gather_predictions` (multi_stage.py:368-402) takes a flat argmax over one row per individual.  With one window per crown
@@ -530,3 +536,67 @@ def predict_map_multistage(predictor, rasters, anchor="center", rows=None, cols=
     res = predict_windows_multistage(predictor, rs, origins, batch_size=batch_size)
     h, w = r1 - r0, c1 - c0
     return res.ens_label.reshape(h, w), res.ens_score.reshape(h, w), res.ens_level.reshape(h, w)
+
+
+def predict_windows_metadata(predictor, raster, site, origins, crown_offsets=None, batch_size=4096, return_probs=False):
+    """predict_windows for the site-metadata fusion model: walks `origins` in batches of `batch_size` -- gather, the sensor
+    model's eval forward, then site branch + fusion layer + softmax + top-2 as ONE launch (dta_meta_predict with the
+    raster's site for every row) writing into row slices of the preallocated outputs; nothing inside the loop waits for the
+    device.  predictor: an engine.MetadataPredictor (its table is built once, before the loop).  raster: a DenseRaster in
+    the form raster_precision(predictor.sensor) names.  site: the raster's site index, one int.
+    Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None) as predict_windows does."""
+    from .engine import MetadataPredictor
+    if not isinstance(predictor, MetadataPredictor):
+        raise TypeError("the metadata route needs an engine.MetadataPredictor")
+    if not isinstance(raster, DenseRaster):
+        raise TypeError("raster must be a DenseRaster")
+    sens = predictor.sensor
+    want = raster_precision(sens)
+    if raster.precision != want:
+        raise RuntimeError("this network reads a DenseRaster(..., precision={!r}) (dense.raster_precision)".format(want))
+    site = int(site)
+    if not 0 <= site < predictor.sites:
+        raise ValueError("site {} is outside [0, {})".format(site, predictor.sites))
+    dev, size = raster.device, WINDOW
+    o = raster._origins(origins)
+    N, classes = o.shape[0], predictor.classes
+    if crown_offsets is not None:
+        crown_offsets = _host_offsets(crown_offsets, N)
+    B = min(int(batch_size), N)
+    if B < 1:
+        raise ValueError("batch_size must be positive")
+    keep = return_probs or crown_offsets is not None
+    top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
+    top_score = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
+    tiles = want == "bf16"
+    if tiles:
+        per = ((raster.bands + 15) // 16) * size * size * 16
+        buf = torch.empty(B * per, dtype=torch.int16, device=dev)
+    else:
+        buf = torch.empty(B, raster.bands, size, size, dtype=torch.float32, device=dev)
+    ws = predictor.table()
+    for n0 in range(0, N, B):
+        n = min(B, N - n0)
+        ob = o[n0:n0 + n]
+        x = raster.windows(ob, tiles=True, size=size, out=buf[:n * per]) if tiles else raster.windows(ob, size=size, out=buf[:n])
+        scores = sens.logits_of(x)
+        predictor.head(scores, n, ws, site, None, probs[n0:n0 + n] if keep else None, top_idx[n0:n0 + n], top_score[n0:n0 + n])
+    crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
+    return WindowPredictions(top_idx, top_score, probs if return_probs else None, crowns)
+
+
+def predict_map_metadata(predictor, raster, site, anchor="center", rows=None, cols=None, clip=10, batch_size=4096):
+    """predict_map for the site-metadata fusion model: raster is a raw band-first array or a DenseRaster, site its site
+    index.  Returns (labels [h][w] int64, scores [h][w] float32): the top-1 class of each pixel's window and its probability."""
+    from .engine import MetadataPredictor
+    if not isinstance(predictor, MetadataPredictor):
+        raise TypeError("the metadata route needs an engine.MetadataPredictor")
+    if not isinstance(raster, DenseRaster):
+        raster = DenseRaster(raster, clip=clip, precision=raster_precision(predictor.sensor), device=predictor.device)
+    r0, r1 = rows if rows is not None else (0, raster.height)
+    c0, c1 = cols if cols is not None else (0, raster.width)
+    origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
+    res = predict_windows_metadata(predictor, raster, site, origins, batch_size=batch_size)
+    h, w = r1 - r0, c1 - c0
+    return res.top_idx[:, 0].reshape(h, w), res.top_score[:, 0].reshape(h, w)

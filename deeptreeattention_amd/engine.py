@@ -1924,6 +1924,14 @@ class MetadataTrainer(_SingleModelMetrics):
                 return self._metrics_step(out.float(), self.sensor._labels(y), None, top_k, self.sensor.device)
             return torch.nn.functional.cross_entropy(out, self.sensor._labels(y))
 
+    def predict_step(self, batch, batch_idx=0):
+        """batch = (individual, {"HSI": images, "site": site}) -> (individual, probs [B, classes]): the eval-mode softmax
+        scores of the fused model through a cached MetadataPredictor (this trainer's in-place updates are followed)."""
+        individual, inputs = batch
+        if getattr(self, "_predictor", None) is None:
+            self._predictor = MetadataPredictor(self.model)
+        return individual, self._predictor(inputs["HSI"], inputs["site"], True)[0].clone()
+
 
 class Predictor:
     """Inference step of the reference (`MultiStage.predict_step` src/models/multi_stage.py:306-318,
@@ -2113,6 +2121,119 @@ class Predictor:
                                       _lib.ptr(self.top_idx), _lib.ptr(self.top_score), _lib.current_stream_ptr()),
                    "dta_softmax_top2")
         return (self.probs if return_probs else None), self.top_idx, self.top_score
+
+
+class MetadataPredictor:
+    """Inference with the site-metadata fusion model (metadata.metadata_sensor_fusion): the sensor model's eval forward
+    (a Predictor on model.sensor_model; `images` may be a preprocess.PatchTiles for a bf16-mode model), then the whole head --
+    site branch, fusion layer, softmax, top-2 -- as dta_meta_site_table + ONE dta_meta_predict launch (csrc/meta.hip; the
+    formulas: metadata.site_table_np / fuse_predict_np).  Always eval mode, whatever the module's flag says: running
+    statistics are read, nothing of the model is written.
+    frozen=False: the table launch runs on every call, so in-place updates (MetadataTrainer) are followed.
+    frozen=True: the table and the sensor's weight re-layouts of the first call are kept; refresh() rebuilds them."""
+
+    def __init__(self, model, frozen=False):
+        import weakref
+        from .metadata import metadata_sensor_fusion
+        if not isinstance(model, metadata_sensor_fusion):
+            raise TypeError("MetadataPredictor needs a deeptreeattention_amd.metadata.metadata_sensor_fusion")
+        self.frozen = bool(frozen)
+        self._model_ref = weakref.ref(model)
+        self.sensor = Predictor(model.sensor_model, frozen=frozen)
+        self.device = self.sensor.device
+        self._ws = None          # (key, workspace): T [sites][classes] + the re-laid-out HSI half of fc1.weight
+        self._tabled = None      # frozen: the parameter addresses the kept table was built from
+        self._bufs = None        # (batch, out, probs, top_idx, top_score)
+
+    @property
+    def model(self):
+        return self._model_ref()
+
+    @property
+    def classes(self):
+        return self.model.fc1.out_features
+
+    @property
+    def sites(self):
+        return self.model.metadata_model.embedding.num_embeddings
+
+    @property
+    def fused_scores(self):
+        """The last call's fused scores (B, classes): what model(images, site) returns in eval mode."""
+        return None if self._bufs is None else self._bufs[1]
+
+    def refresh(self):
+        self.sensor.refresh()
+        self._tabled = None
+
+    def _params(self):
+        m = self.model
+        mm, fc = m.metadata_model, m.fc1
+        bn = mm.batch_norm
+        if not bn.track_running_stats or bn.running_mean is None or not bn.affine:
+            raise RuntimeError("MetadataPredictor supports the reference's BatchNorm1d settings (affine, running statistics)")
+        ts = [mm.embedding.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, mm.mlp.weight, mm.mlp.bias, fc.weight, fc.bias]
+        for t in ts:
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise RuntimeError("MetadataPredictor needs the whole model in contiguous float32 on the sensor model's device")
+        if fc.in_features != 2 * fc.out_features or mm.mlp.out_features != fc.out_features or mm.embedding.embedding_dim != 16:
+            raise RuntimeError("MetadataPredictor needs the reference's head: a 16-wide site branch and a 2 * classes -> classes fusion layer")
+        p = [t.data_ptr() for t in ts]
+        return _lib.MetaParams(p[0], p[1], p[2], p[3], p[4], None, p[5], p[6], p[7], p[8]), tuple(p), float(bn.eps)
+
+    def table(self):
+        """The workspace with T and the re-laid-out fusion weights: built by this call (dta_meta_site_table), or with
+        frozen=True the one kept from the first call."""
+        L = _lib.lib()
+        classes, sites = self.classes, self.sites
+        P, addrs, eps = self._params()
+        key = (classes, sites)
+        if self._ws is None or self._ws[0] != key:
+            nbytes = L.dta_meta_predict_workspace_bytes(classes, sites)
+            if nbytes == 0:
+                raise RuntimeError("dta_meta_predict_workspace_bytes: " + L.dta_last_error().decode())
+            self._ws = (key, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
+            self._tabled = None
+        ws = self._ws[1]
+        if not (self.frozen and self._tabled == addrs):
+            _lib.check(L.dta_meta_site_table(classes, sites, eps, C.byref(P), _lib.ptr(ws), _lib.current_stream_ptr()),
+                       "dta_meta_site_table")
+            self._tabled = addrs
+        return ws
+
+    def site_arg(self, site, rows):
+        """(device pointer or None, site for every row) of dta_meta_predict, and the tensor that must outlive the launch."""
+        if isinstance(site, torch.Tensor):
+            s = site if (site.dtype == torch.int64 and site.device == self.device and site.is_contiguous()) \
+                else site.to(self.device, torch.int64).contiguous()
+            if tuple(s.shape) != (rows,):
+                raise ValueError("site must be one int or an int64 tensor [{}], got shape {}".format(rows, tuple(s.shape)))
+            return _lib.ptr(s), 0, s
+        s = int(site)
+        if not 0 <= s < self.sites:
+            raise ValueError("site {} is outside [0, {})".format(s, self.sites))
+        return None, s, None
+
+    def head(self, scores, rows, ws, site, out, probs, top_idx, top_score):
+        """dta_meta_predict on the first `rows` rows of the HSI scores, into the caller's buffers (out / probs may be None)."""
+        sp, s_all, keep = self.site_arg(site, rows)
+        _lib.check(_lib.lib().dta_meta_predict(rows, self.classes, self.sites, _lib.ptr(ws), sp, s_all, _lib.ptr(scores), _lib.ptr(out),
+                                               _lib.ptr(probs), _lib.ptr(top_idx), _lib.ptr(top_score), _lib.current_stream_ptr()),
+                   "dta_meta_predict")
+
+    def __call__(self, images, site, return_probs=True):
+        """images (B, bands, 11, 11) float32 or a PatchTiles, site: an int64 tensor [B] or one Python int.
+        Returns (probs or None, top_idx [B,2] int64, top_score [B,2] float32); buffers are reused across calls."""
+        scores = self.sensor.logits_of(images)
+        B, classes = scores.shape
+        if classes != self.classes:
+            raise RuntimeError("the sensor model scores {} classes, the fusion layer {}".format(classes, self.classes))
+        if self._bufs is None or self._bufs[0] != B:
+            f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+            self._bufs = (B, f(B, classes), f(B, classes), torch.empty(B, 2, dtype=torch.int64, device=self.device), f(B, 2))
+        _, out, probs, top_idx, top_score = self._bufs
+        self.head(scores, B, self.table(), site, out, probs if return_probs else None, top_idx, top_score)
+        return (probs if return_probs else None), top_idx, top_score
 
 
 class MultiStagePredictor:

@@ -595,6 +595,23 @@ int dta_meta_head_backward(int batch, int classes, int sites, int training, cons
                            const float* drop, void* workspace, const float* out, const float* dout, const dta_meta_grads* grads,
                            float* dscores, void* stream);
 
+/* Prediction with the fusion model (eval mode: running statistics, no dropout).  The site branch then depends on the site
+ * alone, so fc1's first `classes` columns contribute one bias row per site:
+ *   T[s][c]   = fc_b[c] + sum_j fc_w[c][j] * ReLU(mlp_b[j] + sum_f mlp_w[j][f] * bn(emb[s][f]))      j < classes, f < 16
+ *   out[b][c] = ReLU(T[site_b][c] + sum_k fc_w[c][classes + k] * scores[b][k])                       k < classes
+ * dta_meta_site_table writes T and the re-laid-out HSI half of fc_w into the caller's workspace (one launch; reads the
+ * running statistics, writes nothing else; any number of sites up to 2^20).  dta_meta_predict is then ONE launch per batch:
+ * fused scores, softmax and top-2 (dta_softmax_top2's rule: value descending, ties to the lower class).  2 <= classes <= 1020.
+ * site: int64 [batch] on the device, or NULL: every row has site `site_all` (a raster has one site), which is then checked
+ * here.  A row whose site is outside [0, sites) gets top_idx -1, top_score 0 and zero out / probs rows (dta_crown_reduce's
+ * empty-crown convention); nothing is read out of bounds.  out / probs [batch][classes] may be NULL.  top_idx [batch][2]
+ * int64, top_score [batch][2] float32.  Each (row, class) is one float32 accumulator over k ascending, no atomics: a row's
+ * bits do not depend on the batch size or on its place in the batch.  The workspace must be 16-byte aligned. */
+size_t dta_meta_predict_workspace_bytes(int classes, int sites);
+int dta_meta_site_table(int classes, int sites, float eps, const dta_meta_params* p, void* workspace, void* stream);
+int dta_meta_predict(int batch, int classes, int sites, const void* workspace, const long long* site, long long site_all,
+                     const float* scores, float* out, float* probs, long long* top_idx, float* top_score, void* stream);
+
 /* ---- Dense per-pixel window prediction over a raster (reference src/patches.py:50-83 `bounds_to_pixel`: one 11x11 window
  * per pixel of a crown box, read with boundless=True; src/main.py:165-178).  The preprocessing above is per pixel position
  * and a size x size window resized to size x size is the identity, so the preprocessed window equals the window of the
