@@ -261,7 +261,16 @@ int dta_attention_backward(const dta_attention_desc* d, const float* const param
     GemmGroup grp;
     for (int which = 0; which < 2; ++which) {
       float* gw = grads[which * 2];
-      if (!gw) continue;
+      if (!gw) {   // only the weight entry is skipped: its bias gradient is the batch sum of the same vector (d1 / d2)
+        if (grads[which * 2 + 1]) {
+          ColsumArgs cb;
+          memset(&cb, 0, sizeof(cb));
+          cb.A = vec + (which ? 0 : 2 * C); cb.rows = B; cb.cols = C; cb.lda = ld; cb.nseg = 1;
+          cb.off[0] = 0; cb.len[0] = C; cb.dst[0] = grads[which * 2 + 1]; cb.dst_stride[0] = 1;
+          if (launch_colsum_scatter(cb, st)) return 1;
+        }
+        continue;
+      }
       GemmArgs ga;
       memset(&ga, 0, sizeof(ga));
       ga.A = vec + (which ? 0 : 2 * C); ga.sa_m = 1; ga.sa_k = ld;
@@ -292,7 +301,7 @@ int dta_linear_forward(const float* x, const float* w, const float* b, int batch
   ga.Bm = w; ga.sb_k = 1; ga.sb_n = in_features;
   ga.C = out; ga.sc_m = out_features; ga.sc_n = 1; ga.bias = b;
   ga.M = batch; ga.N = out_features; ga.K = in_features; ga.ksplit = gemm_auto_ksplit(batch, out_features, in_features);
-  if (ga.ksplit > 1) hipMemsetAsync(out, 0, (size_t)batch * out_features * 4, (hipStream_t)stream);
+  if (gemm_planned_ksplit(ga) > 1) hipMemsetAsync(out, 0, (size_t)batch * out_features * 4, (hipStream_t)stream);
   return launch_gemm(ga, (hipStream_t)stream);
 }
 
@@ -307,7 +316,7 @@ int dta_linear_backward(const float* x, const float* w, const float* dout, int b
     ga.Bm = w; ga.sb_k = in_features; ga.sb_n = 1;
     ga.C = dx; ga.sc_m = in_features; ga.sc_n = 1;
     ga.M = batch; ga.N = in_features; ga.K = out_features; ga.ksplit = gemm_auto_ksplit(batch, in_features, out_features);
-    if (ga.ksplit > 1) hipMemsetAsync(dx, 0, (size_t)batch * in_features * 4, st);
+    if (gemm_planned_ksplit(ga) > 1) hipMemsetAsync(dx, 0, (size_t)batch * in_features * 4, st);
     if (launch_gemm(ga, st)) return 1;
   }
   if (gw) {   // gw / gb arrive zero-filled

@@ -617,7 +617,8 @@ static int launch_conv_bf16_t(ConvArgs a, int G, hipStream_t st) {
     if (epi > lds) lds = epi;
   }
   if (lds > 160 * 1024) { dta_set_error("conv3x3(bf16): LDS need %zu B exceeds 160 KiB (H=%d W=%d)", lds, a.H, a.W); return 1; }
-  if (a.ppw * a.Q * 2 > 4 * NW * 64) { dta_set_error("conv3x3(bf16): %dx%d tile exceeds the staging plan", a.H, a.W); return 1; }
+  // (four 16-byte vectors per thread stage a workgroup's input tiles: the patches it really holds, at most B of them)
+  if ((a.ppw < a.B ? a.ppw : a.B) * a.Q * 2 > 4 * NW * 64) { dta_set_error("conv3x3(bf16): %dx%d tile exceeds the staging plan", a.H, a.W); return 1; }
   static DevOnce attr_once;      // (function attributes are per device)
   if (attr_once.first()) {
     hipFuncSetAttribute((const void*)k_conv3x3_bf16<MT, NT, false, NW, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

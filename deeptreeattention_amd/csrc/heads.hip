@@ -388,9 +388,12 @@ int gemm_auto_ksplit(int M, int N, int K) {
 
 // wave-tile GEMMs split K inside the workgroup: no cross-workgroup split (and so no atomics, no pre-zeroed output,
 // run-to-run identical sums) unless K is huge
+int gemm_planned_ksplit(const GemmArgs& a) {
+  if (gemm_wave_tiles(a) && a.K <= 8192) return 1;
+  return a.ksplit < 1 ? 1 : a.ksplit;
+}
 static void gemm_group_plan(GemmGroup& gg) {
-  for (int i = 0; i < gg.n; ++i)
-    if (gemm_wave_tiles(gg.g[i]) && gg.g[i].K <= 8192) gg.g[i].ksplit = 1;
+  for (int i = 0; i < gg.n; ++i) gg.g[i].ksplit = gemm_planned_ksplit(gg.g[i]);
 }
 
 int launch_gemm_group(GemmGroup& gg, hipStream_t st) {

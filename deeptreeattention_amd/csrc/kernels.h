@@ -463,6 +463,9 @@ int launch_gemm_group(GemmGroup& gg, hipStream_t st);
 // wide: the GEMM workgroups are 16 waves (the bf16 step: -1.5 us); false: four waves (the fp32 step measured 0.3 % slower wide)
 int launch_gemm_group_with_reduce(GemmGroup& gg, WgradReduceGroup& gr, hipStream_t st, bool wide = false);
 int gemm_auto_ksplit(int M, int N, int K);
+// the K split the launch will actually use for `a` (a.ksplit as the caller set it): 1 for wave-tile problems with K <= 8192.
+// ksplit > 1 accumulates with atomics, so the caller clears C exactly when this is > 1
+int gemm_planned_ksplit(const GemmArgs& a);
 struct ColsumArgs {
   const float* A; int rows, cols; long lda;
   int nseg; int off[8], len[8]; float* dst[8]; long dst_stride[8];
