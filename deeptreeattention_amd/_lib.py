@@ -287,6 +287,18 @@ def lib():
         L.dta_crown_resolve.restype = C.c_int
         L.dta_crown_resolve.argtypes = [C.c_int, C.POINTER(C.c_void_p), vp, C.c_int, C.POINTER(HierarchyTable), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, vp, vp, vp, vp, vp]
+        # the first conv once per raster (dense_conv1.hip)
+        L.dta_conv1_table_bytes.restype = C.c_int
+        L.dta_conv1_table_bytes.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.dta_raster_conv1_table.restype = C.c_int
+        L.dta_raster_conv1_table.argtypes = [C.POINTER(NetDesc), C.POINTER(SubnetParams), vp, C.c_int, C.c_int, vp, vp, vp]
+        L.dta_gather_conv1_windows.restype = C.c_int
+        L.dta_gather_conv1_windows.argtypes = [C.POINTER(NetDesc), vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]
+        L.dta_conv1_output_range.restype = C.c_int
+        L.dta_conv1_output_range.argtypes = [C.POINTER(NetDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.dta_conv1_forward.restype = C.c_int
+        L.dta_conv1_forward.argtypes = [C.POINTER(NetDesc), C.POINTER(SubnetParams), C.c_void_p, C.c_void_p,
+                                            C.POINTER(ScoreTable), C.c_void_p, C.c_void_p]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

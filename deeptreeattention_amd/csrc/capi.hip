@@ -94,6 +94,9 @@ struct Carver {
 // input-gradient convs of layers 2 and 3
 constexpr size_t CONV_TAB_BYTES = (size_t)2 * 576 * 4;
 
+// storage of the conv outputs between kernels (Plan::y_fmt; the first-conv table of dense_conv1.hip is kept in it too)
+inline int conv_out_fmt(const dta_net_desc* d) { return (d->dtype == DTA_BF16 && !switches().fp32_act) ? FMT_F16 : FMT_F32; }
+
 // All workspace offsets for one network description (identical in forward and backward).
 struct Plan {
   int G, B, bands, H, W, classes, esz;
@@ -136,7 +139,7 @@ int build_plan(const dta_net_desc* d, Plan* p, int years = 0, const int* group_c
   p->shared_x = d->kind == DTA_NET_HANG2020;
   p->B = d->batch; p->bands = d->bands; p->H = d->height; p->W = d->width; p->classes = d->classes;
   p->esz = d->dtype == DTA_BF16 ? 2 : 4;
-  p->y_fmt = (d->dtype == DTA_BF16 && !switches().fp32_act) ? FMT_F16 : FMT_F32;
+  p->y_fmt = conv_out_fmt(d);
   switch (d->kind) {
     case DTA_NET_HANG2020: p->kinds[0] = KIND_SPECTRAL; p->kinds[1] = KIND_SPATIAL; break;
     case DTA_NET_SPECTRAL: p->kinds[0] = KIND_SPECTRAL; break;
@@ -408,6 +411,8 @@ struct FwdOpts {
   const void* x_tiles = nullptr;   // the network input already as halo-free bf16 conv tiles (dta_preprocess_crops_tiles): no fp32 input at all
   const float* gate = nullptr;     // device, per group (year ensembles): a year the step skips keeps its running statistics
   const LossArgs* loss = nullptr;  // the loss in the same call (the fused tail, or the launch dta_net_loss would issue)
+  bool y0_ready = false;           // y[0] (the first conv's output) is already in the workspace (dta_gather_conv1_windows):
+                                   // no input pack job, no row table and no conv launch for layer 0
 };
 struct BwdOpts {
   int phases = 3;                  // bit 0: everything but the first conv's weight gradient, bit 1: that gradient
@@ -433,6 +438,10 @@ int forward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* net
               const float* const* xs, void* ws, float* const (*scores)[3], float* joint, hipStream_t st,
               const FwdOpts& o) {
   const void* x_tiles = o.x_tiles; const float* gate = o.gate; const LossArgs* loss = o.loss;
+  if (o.y0_ready && (d->training || !(d->heads_mask & DTA_FORWARD_ONLY) || p.H != 11 || p.W != 11 || !(p.shared_x || p.G == 1) || x_tiles)) {
+    dta_set_error("a forward on a ready first-conv output needs eval mode, DTA_FORWARD_ONLY, 11x11 patches and a single input tensor");
+    return 1;
+  }
   if (x_tiles && !(p.esz == 2 && p.x_compact && (p.shared_x || p.G == 1))) {
     dta_set_error("input tiles need the bf16 mode, 11x11-class patches and a single input tensor");
     return 1;
@@ -480,14 +489,14 @@ int forward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* net
     PrepArgs pa = {};
     // bf16, halo-free input tiles: the first conv reads the caller's fp32 tensor itself (and leaves the bf16 tiles
     // behind for the weight gradient), so there is no input-pack job
-    pa.nx = (x_tiles || fused_input(p)) ? 0 : (p.shared_x ? 1 : G); pa.x_tl_gs = p.x_tl_gs;
+    pa.nx = (x_tiles || o.y0_ready || fused_input(p)) ? 0 : (p.shared_x ? 1 : G); pa.x_tl_gs = p.x_tl_gs;
     for (int g = 0; g < pa.nx; ++g) pa.x[g] = xs[g];
     pa.x_tl = at<char>(ws, p.x_tl); pa.B = B; pa.C = p.bands; pa.H = p.H; pa.W = p.W;
     pa.x_compact = p.x_compact;
     pa.packs = packs; pa.spacks = spacks;
     if (sizeof(T) == 2 && !reuse) {      // row tables of the step's conv launches (full workgroups read them instead of building their own)
       const bool fan_fwd0 = d->training && (switches().fanin & 1);
-      for (int L = 0; L < 3; ++L) add_conv_tab_job(p, ws, fwd_conv_geom(p, d, L, fan_fwd0), (L == 0 && p.shared_x) ? 1 : G, conv_tab_slot_fwd(L), pa.tabs);
+      for (int L = o.y0_ready ? 1 : 0; L < 3; ++L) add_conv_tab_job(p, ws, fwd_conv_geom(p, d, L, fan_fwd0), (L == 0 && p.shared_x) ? 1 : G, conv_tab_slot_fwd(L), pa.tabs);
       if (d->training && !(d->heads_mask & DTA_FORWARD_ONLY))
         for (int L = 1; L < 3; ++L) add_conv_tab_job(p, ws, dgrad_conv_geom(p, L), G, conv_tab_slot_dgrad(L), pa.tabs);
     }
@@ -532,9 +541,11 @@ int forward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* net
     // DTA_FANIN=1 (experiment, measured SLOWER than the finalize launch it removes: profiles/README.md, round 4): the conv
     // launch folds its BatchNorm partials itself (FAN_R rows of raw sums), the stage workgroups add those up in their prologue
     if (fan_fwd) { ca.fan_count = at<unsigned>(ws, p.fan_ctr) + (size_t)L * MAXG * FAN_R; ca.fan_sums = at<double>(ws, p.fan_fwd[L]); }
-    prof_begin(DTA_SITE_CONV_FWD + L, st);
-    if (launch_conv3x3<T>(ca, launchG, st)) return 1;
-    prof_end(DTA_SITE_CONV_FWD + L, st);
+    if (!(L == 0 && o.y0_ready)) {
+      prof_begin(DTA_SITE_CONV_FWD + L, st);
+      if (launch_conv3x3<T>(ca, launchG, st)) return 1;
+      prof_end(DTA_SITE_CONV_FWD + L, st);
+    }
     // BatchNorm statistics -> per-channel scale/shift
     BnFinalizeArgs bf;
     memset(&bf, 0, sizeof(bf));
@@ -1039,6 +1050,27 @@ int dta_net_forward_tiles(const dta_net_desc* d, const dta_subnet_params* nets, 
   if (d->dtype != DTA_BF16) { dta_set_error("dta_net_forward_tiles: bf16 mode only"); return 1; }
   const float* xs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
   return run_forward(p, d, nets, alpha, xs, workspace, scores, joint, (hipStream_t)stream, {.x_tiles = x_tiles});
+}
+
+int dta_conv1_output_range(const dta_net_desc* d, size_t* offset, size_t* bytes) {
+  Plan p;
+  if (!d || !offset || !bytes) { dta_set_error("dta_conv1_output_range: null argument"); return 1; }
+  if (build_plan(d, &p)) return 1;
+  *offset = p.y[0];
+  *bytes = (size_t)p.B * p.HWc[0] * CH[0] * p.G * fmt_bytes(p.y_fmt);
+  return 0;
+}
+
+int dta_conv1_forward(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, void* workspace,
+                          float* const scores[2][3], float* joint, void* stream) {
+  Plan p;
+  if (!d || !nets || !workspace) { dta_set_error("dta_conv1_forward: null argument"); return 1; }
+  if (d->training || !(d->heads_mask & DTA_FORWARD_ONLY)) { dta_set_error("dta_conv1_forward: eval mode (training == 0) with DTA_FORWARD_ONLY only"); return 1; }
+  if (d->kind == DTA_NET_VANILLA) { dta_set_error("dta_conv1_forward: Hang2020, spectral_network and spatial_network only"); return 1; }
+  if (d->height != 11 || d->width != 11) { dta_set_error("dta_conv1_forward: 11x11 patches only, not %dx%d", d->height, d->width); return 1; }
+  if (build_plan(d, &p)) return 1;
+  const float* xs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
+  return run_forward(p, d, nets, alpha, xs, workspace, scores, joint, (hipStream_t)stream, {.y0_ready = true});
 }
 
 int dta_net_forward_loss(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, const float* x,
@@ -1649,6 +1681,73 @@ int dta_crown_resolve(int levels, const float* const* probs, const long long* of
   }
   a.n = levels; a.n_crowns = n_crowns; a.offsets = offsets; a.count = count; a.win_label = window_labels; a.votes = votes;
   return launch_crown_resolve(a, (hipStream_t)stream);
+}
+
+// ---- the first conv once per raster (dense_conv1.hip) ----
+namespace {
+struct Conv1Geom { int cols, NC, esz, fmt; size_t wp_bytes, positions; };
+int conv1_geom(const char* who, const dta_net_desc* d, int height, int width, Conv1Geom* g) {
+  if (!d) { dta_set_error("%s: null argument", who); return 1; }
+  if (d->kind != DTA_NET_HANG2020 && d->kind != DTA_NET_SPECTRAL && d->kind != DTA_NET_SPATIAL) { dta_set_error("%s: Hang2020, spectral_network and spatial_network only (kind %d)", who, d->kind); return 1; }
+  if (d->dtype != DTA_BF16 && d->dtype != DTA_F32) { dta_set_error("%s: unknown dtype %d", who, d->dtype); return 1; }
+  if (d->bands < 1 || height < 1 || width < 1) { dta_set_error("%s: bad shape: bands=%d H=%d W=%d", who, d->bands, height, width); return 1; }
+  g->cols = d->kind == DTA_NET_HANG2020 ? 2 * CH[0] : CH[0];
+  g->NC = (d->bands + 15) / 16;
+  g->esz = d->dtype == DTA_BF16 ? 2 : 4;
+  g->fmt = conv_out_fmt(d);
+  g->wp_bytes = ((size_t)g->NC * 9 * g->cols * 16 * g->esz + 255) & ~(size_t)255;
+  g->positions = (size_t)(height + 2) * (width + 2) + 1;
+  return 0;
+}
+}  // namespace
+
+int dta_conv1_table_bytes(const dta_net_desc* d, int height, int width, size_t* scratch_bytes, size_t* table_bytes) {
+  Conv1Geom g;
+  if (!scratch_bytes || !table_bytes) { dta_set_error("dta_conv1_table_bytes: null argument"); return 1; }
+  if (conv1_geom("dta_conv1_table_bytes", d, height, width, &g)) return 1;
+  *scratch_bytes = g.wp_bytes + (size_t)height * width * 9 * g.cols * 4;
+  *table_bytes = g.positions * 9 * g.cols * fmt_bytes(g.fmt);
+  return 0;
+}
+
+int dta_raster_conv1_table(const dta_net_desc* d, const dta_subnet_params* nets, const void* raster, int height, int width,
+                           void* scratch, void* table, void* stream) {
+  const char* who = "dta_raster_conv1_table";
+  Conv1Geom g;
+  if (!nets || !raster || !scratch || !table) { dta_set_error("%s: null argument", who); return 1; }
+  if (conv1_geom(who, d, height, width, &g)) return 1;
+  if (((uintptr_t)raster & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)table & 15)) { dta_set_error("%s: raster, scratch and table must be 16-byte aligned", who); return 1; }
+  const int G = d->kind == DTA_NET_HANG2020 ? 2 : 1;
+  for (int b = 0; b < G; ++b)
+    if (!nets[b].conv_w[0] || !nets[b].conv_b[0]) { dta_set_error("%s: the first conv's parameters are missing", who); return 1; }
+  hipStream_t st = (hipStream_t)stream;
+  // the first conv's forward weight image, exactly as the forward packs it for its own first conv
+  PackWArgs pw;
+  memset(&pw, 0, sizeof(pw));
+  pw.G = 1; pw.NC = g.NC; pw.N = g.cols; pw.K = d->bands; pw.mode = G == 2 ? 1 : 0; pw.nsplit = CH[0];
+  for (int b = 0; b < G; ++b) pw.src[b] = nets[b].conv_w[0];
+  if (d->dtype == DTA_BF16 ? launch_pack_conv_w<bf16_t>(pw, scratch, st) : launch_pack_conv_w<float>(pw, scratch, st)) return 1;
+  float* T = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + g.wp_bytes);
+  Conv1TapsArgs ta;
+  ta.raster = raster; ta.wp = scratch; ta.T = T; ta.P = (long long)height * width; ta.C = d->bands; ta.NC = g.NC; ta.N = 9 * g.cols;
+  if (launch_raster_conv1_taps(ta, d->dtype == DTA_BF16, st)) return 1;
+  Conv1ClassArgs ca;
+  ca.T = T; ca.bias[0] = nets[0].conv_b[0]; ca.bias[1] = G == 2 ? nets[1].conv_b[0] : nets[0].conv_b[0];
+  ca.bias_split = G == 2 ? CH[0] : g.cols; ca.A = table; ca.H = height; ca.W = width; ca.cols = g.cols; ca.fmt = g.fmt;
+  return launch_raster_conv1_classes(ca, st);
+}
+
+int dta_gather_conv1_windows(const dta_net_desc* d, const void* table, int height, int width, const int* origins, int n,
+                             void* y0, void* stream) {
+  const char* who = "dta_gather_conv1_windows";
+  Conv1Geom g;
+  if (!table || !origins || !y0) { dta_set_error("%s: null argument", who); return 1; }
+  if (conv1_geom(who, d, height, width, &g)) return 1;
+  if (n < 1) { dta_set_error("%s: bad shape: n=%d", who, n); return 1; }
+  if (((uintptr_t)table & 15) || ((uintptr_t)y0 & 15)) { dta_set_error("%s: table and output must be 16-byte aligned", who); return 1; }
+  Conv1GatherArgs a;
+  a.A = table; a.origins = origins; a.out = y0; a.N = n; a.H = height; a.W = width; a.ppr = g.cols * fmt_bytes(g.fmt) / 16;
+  return launch_gather_conv1_windows(a, (hipStream_t)stream);
 }
 
 int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns, int classes, float* mean,

@@ -704,4 +704,17 @@ struct CrownResolveArgs { CrownLevel lv[BLEND_CE_MULTI_MAX]; int n, n_crowns; co
                           const long long* win_label; int* votes; HierarchyArgs e; };
 int launch_crown_resolve(const CrownResolveArgs& a, hipStream_t st);
 
+// ---- dense_conv1.hip: the first conv once per raster -------------------------------------------------
+// T float32 [P][N] (N = 9 * cols, column = tap * cols + n) = raster pixels x the first conv's forward weight image wp
+// ([NC][9][cols][16] as k_pack_conv_w leaves it); raster: bf16 chunks [NC][P][16] or float32 planes [C][P]
+struct Conv1TapsArgs { const void* raster; const void* wp; float* T; long long P; int C, NC, N; };
+int launch_raster_conv1_taps(const Conv1TapsArgs& a, bool bf16, hipStream_t st);
+// A [(H + 2) * (W + 2) + 1][9][cols] in `fmt`: the nine class sums of every position of the raster with its ring, then the
+// far-outside row; bias of column n: bias[0][n] below bias_split, else bias[1][n - bias_split]
+struct Conv1ClassArgs { const float* T; const float* bias[2]; int bias_split; void* A; int H, W, cols, fmt; };
+int launch_raster_conv1_classes(const Conv1ClassArgs& a, hipStream_t st);
+// rows [N * 121] of ppr 16-byte pieces each, copied out of A (same piece count per class row)
+struct Conv1GatherArgs { const void* A; const int* origins; void* out; int N, H, W, ppr; };
+int launch_gather_conv1_windows(const Conv1GatherArgs& a, hipStream_t st);
+
 }  // namespace dta

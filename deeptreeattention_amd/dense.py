@@ -35,8 +35,16 @@ The species of a crown with several windows is THIS package's definition: per le
 `gather_predictions` (multi_stage.py:368-402) takes a flat argmax over one row per individual.  With one window per crown
 the definition is the reference's, exactly.
 
+With share_conv1=True (opt-in; single Hang2020 / spectral_network / spatial_network, 11x11) predict_windows / predict_map
+compute the first conv ONCE PER RASTER instead of once per window -- it sits in front of every pool, so its output at a
+window position depends only on the raster pixel underneath and on which taps fall outside the window (nine cases):
+
+    DenseRaster.conv1_table      raster + the network's first conv -> Conv1Table (dta_raster_conv1_table), once per call
+    Conv1Table.gather            origins -> the first conv's output of a batch, written into the Predictor's workspace
+                                 (dta_gather_conv1_windows); the forward then starts behind its first conv (dta_conv1_forward)
+
 `gather_windows_np`, `crown_reduce_np` and `crown_resolve_np` are the written-down meaning of the gather, reduce and
-resolve kernels.
+resolve kernels, `conv1_table_np` and `gather_conv1_np` that of the first-conv table and its gather.
 File reading and georeferencing stay with the caller, as in preprocess.py."""
 import collections
 
@@ -83,6 +91,61 @@ def gather_windows_np(raster_norm, origins, size=WINDOW):
         ra, rb, ca, cb = max(r, 0), min(r + size, Hh), max(c, 0), min(c + size, Ww)
         if ra < rb and ca < cb:
             out[n, :, ra - r:rb - r, ca - c:cb - c] = raster_norm[:, ra:rb, ca:cb]
+    return out
+
+
+Conv1TableNP = collections.namedtuple("Conv1TableNP", "data height width")
+
+
+def conv1_class(i, size=WINDOW):
+    """Which taps of a 3x3 conv fall outside a window of side `size` at row (or column) i of it: 0 = the first row (the
+    tap at -1 is outside), 2 = the last row (the tap at +1 is), 1 = neither."""
+    return 0 if i == 0 else (2 if i == size - 1 else 1)
+
+
+def conv1_table_np(raster_norm, weight, bias):
+    """What dta_raster_conv1_table computes, in the dtype of its arguments (float64 for the definition).
+    raster_norm [C][H][W], weight [cols][C][3][3] (the branches' first-conv weights concatenated along cols), bias [cols].
+        T[q][u][v][n]   = sum_k weight[n][k][u][v] * raster_norm[k][q]                (0 for q outside the raster)
+        A[p][rc][cc][n] = bias[n] + sum_{u in R(rc)} sum_{v in R(cc)} T[p + (u - 1, v - 1)][u][v][n]
+        R(0) = {1, 2} (first row / column of the window), R(1) = {0, 1, 2}, R(2) = {0, 1} (last row / column)
+    each element one accumulator: the bias first, then the taps in ascending (u, v).  Positions p: the raster extended by a
+    one-pixel ring, (H + 2) x (W + 2) row-major, then one far-outside row (every tap on zero input: the bias).
+    Returns Conv1TableNP(data [(H + 2) * (W + 2) + 1][9][cols], H, W); the class index is rc * 3 + cc."""
+    x, w, b = np.asarray(raster_norm), np.asarray(weight), np.asarray(bias)
+    Cb, Hh, Ww = x.shape
+    cols = w.shape[0]
+    if w.shape != (cols, Cb, 3, 3) or b.shape != (cols,):
+        raise ValueError("weight must be [cols][{}][3][3] and bias [cols]".format(Cb))
+    T = np.zeros((Hh + 4, Ww + 4, 3, 3, cols), dtype=x.dtype)         # two pixels of zero around the raster
+    T[2:Hh + 2, 2:Ww + 2] = np.einsum("khw,nkuv->hwuvn", x, w.astype(x.dtype))
+    R = ((1, 2), (0, 1, 2), (0, 1))
+    A = np.empty(((Hh + 2) * (Ww + 2) + 1, 9, cols), dtype=x.dtype)
+    for rc in range(3):
+        for cc in range(3):
+            acc = np.broadcast_to(b.astype(x.dtype), (Hh + 2, Ww + 2, cols)).copy()
+            for u in R[rc]:
+                for v in R[cc]:
+                    acc = acc + T[u:u + Hh + 2, v:v + Ww + 2, u, v]     # position r (from -1) + (u - 1) is padded row r + u + 1
+            A[:-1, rc * 3 + cc] = acc.reshape(-1, cols)
+    A[-1] = b.astype(x.dtype)
+    return Conv1TableNP(A, Hh, Ww)
+
+
+def gather_conv1_np(table, origins, size=WINDOW):
+    """What dta_gather_conv1_windows computes: table = Conv1TableNP (or a Conv1Table read back: Conv1Table.numpy()),
+    origins [N][2] -> [N][size * size][cols]: row i * size + j of window n is table[o_n + (i, j)][rc(i)][cc(j)], a position
+    beyond the ring reading the far-outside row.  A pure copy: the result has the table's dtype and bits."""
+    data, Hh, Ww = table.data, table.height, table.width
+    origins = np.asarray(origins).reshape(-1, 2)
+    out = np.empty((len(origins), size * size, data.shape[2]), dtype=data.dtype)
+    far = (Hh + 2) * (Ww + 2)
+    for n, (r, c) in enumerate(origins):
+        for i in range(size):
+            for j in range(size):
+                rr, cc = int(r) + i, int(c) + j
+                pos = (rr + 1) * (Ww + 2) + (cc + 1) if -1 <= rr <= Hh and -1 <= cc <= Ww else far
+                out[n, i * size + j] = data[pos, conv1_class(i, size) * 3 + conv1_class(j, size)]
     return out
 
 
@@ -222,6 +285,14 @@ class DenseRaster:
         return out
 
 
+    def conv1_table(self, predictor, size=WINDOW):
+        """The first conv of `predictor`'s network over this raster, once (dta_raster_conv1_table): a Conv1Table in the
+        raster's precision, holding the network's weights as they are now.  Raises RuntimeError for what the shared
+        first conv does not cover (_share_conv1_refusals) before anything is launched."""
+        pred = _predictor(predictor)
+        _share_conv1_refusals(pred, self, size)
+        return Conv1Table(self, pred)
+
     @staticmethod
     def windows_years(rasters, origins, outs, flags, clear_next, size=WINDOW):
         """DenseRaster.windows for every year of an ensemble in ONE launch (dta_gather_windows_years).  rasters: one fp32
@@ -249,6 +320,68 @@ class DenseRaster:
         _lib.check(L.dta_gather_windows_years(rp, Y, r0.bands, r0.height, r0.width, _lib.ptr(o), N, size, op, _lib.ptr(flags),
                                               _lib.ptr(clear_next), _lib.current_stream_ptr()), "dta_gather_windows_years")
         return flags
+
+
+def _share_conv1_refusals(pred, raster, size):
+    """What the shared first conv does not cover; raises before anything is launched."""
+    if pred.ensemble:
+        raise RuntimeError("share_conv1: a year ensemble has one input per year, there is no first conv to share")
+    m = pred.nets_mod[0]
+    if m._net_code not in (_lib.NET_HANG2020, _lib.NET_SPECTRAL, _lib.NET_SPATIAL):
+        raise RuntimeError("share_conv1: Hang2020, spectral_network and spatial_network only (not vanilla_CNN)")
+    if m.training:
+        raise RuntimeError("share_conv1: the model is in training mode; prediction runs eval-mode BatchNorm (model.eval())")
+    if size != 11:
+        raise RuntimeError("share_conv1: window side {} -- the first-conv table is laid out for 11x11 windows only".format(size))
+    if not isinstance(raster, DenseRaster):
+        raise TypeError("rasters must be DenseRaster objects")
+    if raster.precision != m.precision:
+        raise RuntimeError("share_conv1: a {}-mode network needs DenseRaster(..., precision={!r}), not {!r}"
+                           .format(m.precision, m.precision, raster.precision))
+    w = next(t for t in m.parameters() if t.dim() == 4)
+    if w.shape[1] != raster.bands:
+        raise ValueError("the network takes {} bands, the normalised raster has {}".format(w.shape[1], raster.bands))
+
+
+class Conv1Table:
+    """The first conv's output for every position a window can put over a raster (module text; csrc/dense_conv1.hip):
+    data [(H + 2) * (W + 2) + 1][9][cols] on the device, IEEE half for a bf16 raster / network, float32 for fp32 -- the
+    storage the forward keeps its first conv's output in.  cols = 64 (Hang2020: spectral | spatial branch) or 32.
+    Built from the network's weights at construction: rebuild it after a weight update."""
+
+    def __init__(self, raster, pred):
+        L = _lib.lib()
+        m = pred.nets_mod[0]
+        self.height, self.width, self.bands, self.precision, self.device = raster.height, raster.width, raster.bands, raster.precision, raster.device
+        self.cols = 64 if m._net_code == _lib.NET_HANG2020 else 32
+        from . import Hang2020 as H
+        self.desc = _lib.NetDesc(1, raster.bands, WINDOW, WINDOW, m._classes, m._net_code, _lib.dtype_code(m.precision), 0,
+                                 4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
+        scratch_b, table_b = _lib.C.c_size_t(), _lib.C.c_size_t()
+        _lib.check(L.dta_conv1_table_bytes(_lib.C.byref(self.desc), self.height, self.width, _lib.C.byref(scratch_b),
+                                           _lib.C.byref(table_b)), "dta_conv1_table_bytes")
+        dt = torch.float16 if self.precision == "bf16" else torch.float32
+        self.data = torch.empty((self.height + 2) * (self.width + 2) + 1, 9, self.cols, dtype=dt, device=self.device)
+        if self.data.numel() * self.data.element_size() != table_b.value:
+            raise RuntimeError("dta_conv1_table_bytes: {} bytes, the binding expects {}".format(table_b.value, self.data.numel() * self.data.element_size()))
+        scratch = torch.empty(scratch_b.value, dtype=torch.uint8, device=self.device)      # T and the weight image: this call only
+        nets = pred._tables([m])[0]
+        _lib.check(L.dta_raster_conv1_table(_lib.C.byref(self.desc), nets, _lib.ptr(raster.data), self.height, self.width,
+                                            _lib.ptr(scratch), _lib.ptr(self.data), _lib.current_stream_ptr()), "dta_raster_conv1_table")
+
+    def gather(self, origins, out):
+        """origins: device int32 [n][2]; out: the bytes that receive [n * 121][cols] (engine.Predictor.conv1_slot)."""
+        n = origins.shape[0]
+        if out.numel() * out.element_size() != n * WINDOW * WINDOW * self.cols * self.data.element_size():
+            raise ValueError("out must hold {} windows x 121 x {} elements".format(n, self.cols))
+        _lib.check(_lib.lib().dta_gather_conv1_windows(_lib.C.byref(self.desc), _lib.ptr(self.data), self.height, self.width,
+                                                       _lib.ptr(origins), n, _lib.ptr(out), _lib.current_stream_ptr()),
+                   "dta_gather_conv1_windows")
+        return out
+
+    def numpy(self):
+        """The table read back, in the form gather_conv1_np takes."""
+        return Conv1TableNP(self.data.cpu().numpy(), self.height, self.width)
 
 
 def _check_years(rs):
@@ -354,7 +487,8 @@ def raster_precision(model_or_predictor):
     return "bf16" if tiles else "fp32"
 
 
-def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False):
+def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False,
+                    share_conv1=False):
     """Per-window prediction on 11x11 windows (the side every prediction route here is tested at; DenseRaster.windows
     gathers other sides): walks `origins` in batches of `batch_size` -- gather, the existing eval forward
     (engine.Predictor), dta_softmax_top2 -- writing top_idx [N, 2] / top_score [N, 2] into preallocated device tensors;
@@ -363,11 +497,20 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
     missing year (an all-zero batch, reference data.py:295-296).
     crown_offsets ([n + 1], windows grouped by crown as window_origins returns them): also the per-crown mean probability
     vector, its top-2 and the window count.  Window probabilities are kept when return_probs or crown_offsets ask for them.
+    share_conv1=True (a single Hang2020 / spectral_network / spatial_network in eval mode; the raster in the MODEL's
+    precision): the first conv is computed once per raster (DenseRaster.conv1_table, built in this call: weight updates
+    between calls are followed) and each batch is a gather of its output into the Predictor's workspace followed by the
+    forward without its first conv -- no window of the input is ever formed.  Anything it does not cover raises
+    RuntimeError before a launch (_share_conv1_refusals).
     Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None)."""
     L = _lib.lib()
     pred = _predictor(model_or_predictor)
-    want = raster_precision(pred)
     size = WINDOW
+    if share_conv1:
+        _share_conv1_refusals(pred, rasters, size)
+        want = rasters.precision
+    else:
+        want = raster_precision(pred)
     if pred.ensemble:
         rs = list(rasters)
         if len(rs) != len(pred.nets_mod):
@@ -394,7 +537,9 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
     probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
     B = min(int(batch_size), N)
     tiles = want == "bf16"
-    if tiles:
+    if share_conv1:
+        table = r0.conv1_table(pred, size=size)
+    elif tiles:
         per = ((r0.bands + 15) // 16) * size * size * 16
         bufs = [torch.empty(B * per, dtype=torch.int16, device=dev)]
     else:
@@ -407,24 +552,31 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
     for n0 in range(0, N, B):
         n = min(B, N - n0)
         ob = o[n0:n0 + n]
-        if tiles:
-            x = r0.windows(ob, tiles=True, size=size, out=bufs[0][:n * per])
+        if share_conv1:
+            table.gather(ob, pred.conv1_slot(n, r0.bands))
+            logits = pred.logits_from_conv1()
         else:
-            xs = [b[:n] if r is None else r.windows(ob, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
-            x = xs if pred.ensemble else xs[0]
-        logits = pred.logits_of(x)
+            if tiles:
+                x = r0.windows(ob, tiles=True, size=size, out=bufs[0][:n * per])
+            else:
+                xs = [b[:n] if r is None else r.windows(ob, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
+                x = xs if pred.ensemble else xs[0]
+            logits = pred.logits_of(x)
         _lib.check(L.dta_softmax_top2(_lib.ptr(logits), n, classes, _lib.ptr(probs[n0:n0 + n]) if keep else None,
                                       _lib.ptr(top_idx[n0:n0 + n]), _lib.ptr(top_score[n0:n0 + n]), st), "dta_softmax_top2")
     crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
     return WindowPredictions(top_idx, top_score, probs if return_probs else None, crowns)
 
 
-def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=None, clip=10, batch_size=4096):
+def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=None, clip=10, batch_size=4096, share_conv1=False):
     """Label every pixel of a raster region: rows / cols are half-open (start, stop) pixel ranges (default: the whole
     raster).  raster: a raw band-first array or a DenseRaster (a list with one per year, None allowed, for an ensemble).
+    share_conv1: as for predict_windows (a raw array is made resident in the model's precision).
     Returns (labels [h][w] int64, scores [h][w] float32): the top-1 class of each pixel's window and its probability."""
     pred = _predictor(model_or_predictor)
-    want = raster_precision(pred)
+    if share_conv1 and pred.ensemble:
+        raise RuntimeError("share_conv1: a year ensemble has one input per year, there is no first conv to share")
+    want = pred.nets_mod[0].precision if share_conv1 else raster_precision(pred)
 
     def resident(r):
         return r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision=want, device=pred.device)
@@ -433,7 +585,7 @@ def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=Non
     r0, r1 = rows if rows is not None else (0, first.height)
     c0, c1 = cols if cols is not None else (0, first.width)
     origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
-    res = predict_windows(pred, rs, origins, batch_size=batch_size)
+    res = predict_windows(pred, rs, origins, batch_size=batch_size, share_conv1=share_conv1)
     h, w = r1 - r0, c1 - c0
     return res.top_idx[:, 0].reshape(h, w), res.top_score[:, 0].reshape(h, w)
 

@@ -1955,6 +1955,7 @@ class Predictor:
         import weakref
         self.frozen = bool(frozen)
         self._packed = False
+        self._packed_conv1 = False
         from .year import learned_ensemble
         self._model_ref = weakref.ref(model)        # no strong reference: the cache must not keep the model alive
         self.ensemble = isinstance(model, learned_ensemble)
@@ -2037,6 +2038,7 @@ class Predictor:
         self.desc_reuse = _lib.NetDesc(B, bands, Hh, Ww, m0._classes, m0._net_code, _lib.dtype_code(m0.precision), 0,
                                        4 | _lib.FORWARD_ONLY | _lib.REUSE_PACKED, H.BN_MOMENTUM, H.BN_EPS)
         self._packed = False
+        self._packed_conv1 = False
         tables = self._tables([nets_mod[i] for i in kept])
         if self.ensemble:
             self.nets = (_lib.SubnetParams * len(kept))(*[t[0] for t in tables])
@@ -2110,6 +2112,37 @@ class Predictor:
         _lib.check(fwd(C.byref(self._desc()), self.nets, alpha, _lib.ptr(x if tiles is None else tiles), _lib.ptr(self.ws),
                        C.byref(table), joint, st), "dta_net_forward" if tiles is None else "dta_net_forward_tiles")
         self._packed = True
+        return self.logits
+
+    def conv1_slot(self, n, bands):
+        """The place of the first conv's output inside this Predictor's workspace for a batch of n 11x11 windows (the
+        workspace is (re)built for that batch shape): a uint8 view of it, for dta_gather_conv1_windows to fill
+        (dense.Conv1Table.gather).  Single networks only."""
+        if self.ensemble:
+            raise RuntimeError("a year ensemble has one input per year: no shared first conv (dense.predict_windows(share_conv1=True))")
+        self._prepare((int(n), int(bands), 11, 11), [0])
+        off, nbytes = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.lib().dta_conv1_output_range(C.byref(self.desc), C.byref(off), C.byref(nbytes)), "dta_conv1_output_range")
+        return self.ws[off.value:off.value + nbytes.value]
+
+    def logits_from_conv1(self):
+        """Eval-mode scores of the batch whose first-conv output is already in the workspace (conv1_slot, filled by
+        dta_gather_conv1_windows): the forward without its first conv (dta_conv1_forward).  The returned tensor is reused
+        by the next call."""
+        L = _lib.lib()
+        m = self.nets_mod[0]
+        table = _lib.ScoreTable()
+        joint = _lib.ptr(self.logits)
+        if not self.single:
+            table[0][2] = self.logits.data_ptr()
+            joint = None
+        alpha = _lib.ptr(m.alpha) if m._net_code == _lib.NET_HANG2020 else None
+        # frozen weights: this call leaves every re-layout but the first layer's row table behind, so it may reuse what a
+        # call of either kind packed, while the full forward (logits_of) reuses only what a full forward packed
+        reuse = self.frozen and (self._packed or self._packed_conv1)
+        _lib.check(L.dta_conv1_forward(C.byref(self.desc_reuse if reuse else self.desc), self.nets, alpha, _lib.ptr(self.ws),
+                                       C.byref(table), joint, _lib.current_stream_ptr()), "dta_conv1_forward")
+        self._packed_conv1 = True
         return self.logits
 
     def __call__(self, images, return_probs=True, present=None):

@@ -676,6 +676,47 @@ int dta_crown_resolve(int levels, const float* const* probs, const long long* of
                       int* count, long long* ens_label, float* ens_score, int* ens_level, const long long* window_labels,
                       int* votes, void* stream);
 
+/* ---- Dense prediction with the first conv computed ONCE PER RASTER instead of once per window.  The first 3x3 conv sits
+ * in front of every pool, so its output at a window position depends only on the raster pixel p under that position and on
+ * which taps fall outside the window: one of nine classes, (top / middle / bottom row) x (left / middle / right column).
+ *   T[q][dy][dx][n]  = sum_k w[n][k][dy+1][dx+1] * x[k][q]                 (one GEMM over the raster's pixels; 0 outside it)
+ *   A[p][rc][cc][n]  = bias[n] + sum_{dy in R(rc)} sum_{dx in R(cc)} T[p + (dy, dx)][dy][dx][n]
+ *   R(top / left) = {0, +1},  R(middle) = {-1, 0, +1},  R(bottom / right) = {-1, 0}
+ *   conv1(window at origin o)[i][j][n] = A[o + (i, j)][rc(i)][cc(j)][n],   rc(i) = top if i == 0, bottom if i == 10, else middle
+ * This is exact.  Only 11x11 windows; d->kind DTA_NET_HANG2020 (64 columns: spectral | spatial branch, as the forward
+ * concatenates them), DTA_NET_SPECTRAL or DTA_NET_SPATIAL (32 columns).  Of d these calls read kind, dtype and bands (the
+ * raster's NORMALISED band count); the raster is in the form of its dtype: DTA_BF16 the chunk form of dta_raster_normalise
+ * (tiles != 0), DTA_F32 the float32 planes.
+ *
+ * The table: [(height + 2) * (width + 2) + 1][9][cols] -- the positions of the raster extended by a one-pixel ring,
+ * row-major, then one "far outside" row (a position two or more pixels outside has every tap on zero input: the bias), the
+ * class index rc * 3 + cc -- stored as the forward stores its first conv's output: IEEE half in bf16 mode, float32 in fp32
+ * mode.  Each element is ONE float32 accumulator: the bias first, then the taps in ascending (dy, dx); no atomics.
+ * dta_conv1_table_bytes: the sizes of the scratch (the weight image and T, only needed during dta_raster_conv1_table) and
+ * of the table.  A 256x256 raster with 64 columns: 151 MB of scratch, 77 MB of table in half. */
+int dta_conv1_table_bytes(const dta_net_desc* d, int height, int width, size_t* scratch_bytes, size_t* table_bytes);
+/* nets: the network's parameter table (2 entries for Hang2020, else 1); reads conv_w[0] and conv_b[0] of each.  raster,
+ * scratch and table 16-byte aligned.  Three launches (weight image, tap GEMM, class sums), once per raster and weight state. */
+int dta_raster_conv1_table(const dta_net_desc* d, const dta_subnet_params* nets, const void* raster, int height, int width,
+                           void* scratch, void* table, void* stream);
+/* The first conv's output of n windows: row m * 121 + i * 11 + j of y0 ([n * 121][cols], row stride cols) receives the cols
+ * values of A[o_m + (i, j)][rc(i)][cc(j)] -- a pure copy in 16-byte pieces, so y0 holds the table's bits.  origins [n][2]
+ * int32 (row, col) as for dta_gather_windows: anywhere, negative or past the raster.  y0: normally workspace + offset of
+ * dta_conv1_output_range for a descriptor of batch n. */
+int dta_gather_conv1_windows(const dta_net_desc* d, const void* table, int height, int width, const int* origins, int n,
+                             void* y0, void* stream);
+/* Where the forward keeps its first conv's output inside the workspace of `d`: byte offset and size
+ * (batch * height * width rows of cols elements in the storage format above). */
+int dta_conv1_output_range(const dta_net_desc* d, size_t* offset, size_t* bytes);
+/* dta_net_forward for a workspace whose first-conv output is ALREADY in place (dta_gather_conv1_windows): no input, no
+ * input pack job, no row table and no conv launch for the first layer; everything behind it is dta_net_forward's.  Eval
+ * mode (training == 0) with DTA_FORWARD_ONLY, 11x11 patches, kinds as above; anything else is refused.  With
+ * DTA_REUSE_PACKED the usual contract holds, with one addition: this call does not leave the first layer's row table in
+ * the workspace: a dta_net_forward / dta_net_forward_tiles carrying DTA_REUSE_PACKED must still follow one of those two
+ * calls WITHOUT the flag on that workspace (this call with the flag may follow any of the three without it). */
+int dta_conv1_forward(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, void* workspace,
+                          float* const scores[2][3], float* joint, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
