@@ -299,6 +299,27 @@ def lib():
         L.dta_conv1_forward.restype = C.c_int
         L.dta_conv1_forward.argtypes = [C.POINTER(NetDesc), C.POINTER(SubnetParams), C.c_void_p, C.c_void_p,
                                             C.POINTER(ScoreTable), C.c_void_p, C.c_void_p]
+        # ... for the levels x years of a multi-stage model
+        L.dta_conv1_multistage_table_bytes.restype = C.c_int
+        L.dta_conv1_multistage_table_bytes.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t),
+                                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.dta_conv1_multistage_raster_table.restype = C.c_int
+        L.dta_conv1_multistage_raster_table.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(SubnetParams), vp, C.c_int, C.c_int,
+                                                        vp, vp, vp, vp]
+        L.dta_conv1_multistage_output_range.restype = C.c_int
+        L.dta_conv1_multistage_output_range.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(C.c_size_t),
+                                                        C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.dta_conv1_multistage_gather_windows.restype = C.c_int
+        L.dta_conv1_multistage_gather_windows.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.c_int, C.POINTER(C.c_void_p),
+                                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, vp, C.c_int,
+                                                          vp, vp, vp, vp]
+        L.dta_conv1_multistage_predict.restype = C.c_int
+        L.dta_conv1_multistage_predict.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams), vp, vp,
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp]
+        L.dta_conv1_multistage_predict_ensemble.restype = C.c_int
+        L.dta_conv1_multistage_predict_ensemble.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams),
+                                                            vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                            C.POINTER(C.c_void_p), C.POINTER(HierarchyTable), vp, vp, vp, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -411,8 +411,9 @@ struct FwdOpts {
   const void* x_tiles = nullptr;   // the network input already as halo-free bf16 conv tiles (dta_preprocess_crops_tiles): no fp32 input at all
   const float* gate = nullptr;     // device, per group (year ensembles): a year the step skips keeps its running statistics
   const LossArgs* loss = nullptr;  // the loss in the same call (the fused tail, or the launch dta_net_loss would issue)
-  bool y0_ready = false;           // y[0] (the first conv's output) is already in the workspace (dta_gather_conv1_windows):
-                                   // no input pack job, no row table and no conv launch for layer 0
+  bool y0_ready = false;           // y[0] (the first conv's output) is already in the workspace (dta_gather_conv1_windows, or
+                                   // dta_conv1_multistage_gather_windows for every group of a grouped plan): no input pack
+                                   // job, no row table and no conv launch for layer 0
 };
 struct BwdOpts {
   int phases = 3;                  // bit 0: everything but the first conv's weight gradient, bit 1: that gradient
@@ -438,8 +439,8 @@ int forward_t(const Plan& p, const dta_net_desc* d, const dta_subnet_params* net
               const float* const* xs, void* ws, float* const (*scores)[3], float* joint, hipStream_t st,
               const FwdOpts& o) {
   const void* x_tiles = o.x_tiles; const float* gate = o.gate; const LossArgs* loss = o.loss;
-  if (o.y0_ready && (d->training || !(d->heads_mask & DTA_FORWARD_ONLY) || p.H != 11 || p.W != 11 || !(p.shared_x || p.G == 1) || x_tiles)) {
-    dta_set_error("a forward on a ready first-conv output needs eval mode, DTA_FORWARD_ONLY, 11x11 patches and a single input tensor");
+  if (o.y0_ready && (d->training || !(d->heads_mask & DTA_FORWARD_ONLY) || p.H != 11 || p.W != 11 || x_tiles)) {
+    dta_set_error("a forward on a ready first-conv output needs eval mode, DTA_FORWARD_ONLY and 11x11 patches");
     return 1;
   }
   if (x_tiles && !(p.esz == 2 && p.x_compact && (p.shared_x || p.G == 1))) {
@@ -1128,6 +1129,11 @@ static int grouped_forward(const Grouped& g, const dta_subnet_params* nets, cons
                            void* workspace, hipStream_t st) {
   return run_forward(g.p, &g.dd, nets, nullptr, x, workspace, nullptr, nullptr, st, {.gate = gate});
 }
+// ... behind first convs that are already in every group's y[0] (dta_conv1_multistage_gather_windows): no inputs
+static int grouped_forward_conv1(const Grouped& g, const dta_subnet_params* nets, const float* gate, void* workspace, hipStream_t st) {
+  const float* none[MAXG] = {};
+  return run_forward(g.p, &g.dd, nets, nullptr, none, workspace, nullptr, nullptr, st, {.gate = gate, .y0_ready = true});
+}
 // ... and the backward: `dsc` holds each group's last-head score gradient (dsc_level), nothing else carries one
 static int grouped_backward(const Grouped& g, const dta_subnet_params* nets, void* workspace, const float* const (*dsc)[3],
                             const dta_subnet_grads* grads, hipStream_t st, const BwdOpts& o) {
@@ -1313,16 +1319,48 @@ int dta_multistage_forward(const dta_net_desc* d, int levels, const dta_level* l
   return 0;
 }
 
+static int hierarchy_args(const char* who, int levels, const dta_hierarchy* h, long long* ens_label, float* ens_score, int* ens_level,
+                          const long long* labels, long long* confusion, HierarchyArgs* e);
+// The two prediction calls, from the inputs (x) or -- x == NULL by construction, conv1 set -- from first convs already in
+// the workspace: checks, the grouped forward, ONE epilogue launch (with the walk when `table` is given).
+struct EnsembleOut { const dta_hierarchy* table; long long* ens_label; float* ens_score; int* ens_level; const long long* labels; long long* confusion; };
+static int conv1_desc(const char* who, const dta_net_desc* d) {
+  if (!d) { dta_set_error("%s: null argument", who); return 1; }
+  if (d->training || !(d->heads_mask & DTA_FORWARD_ONLY)) { dta_set_error("%s: eval mode (training == 0) with DTA_FORWARD_ONLY only", who); return 1; }
+  if (d->height != 11 || d->width != 11) { dta_set_error("%s: 11x11 patches only, not %dx%d", who, d->height, d->width); return 1; }
+  return 0;
+}
+static int multistage_predict_impl(const char* who, bool conv1, const dta_net_desc* d, int levels, const dta_level* lv,
+                                   const dta_subnet_params* nets, const float* const* x, const float* gate, void* workspace,
+                                   float* const* probs, long long* const* top_idx, float* const* top_score,
+                                   const EnsembleOut* ens, void* stream) {
+  Grouped g; HierarchyArgs e;
+  hipStream_t st = (hipStream_t)stream;
+  if (!nets || (!conv1 && !x) || !workspace || !top_idx || !top_score) { dta_set_error("%s: null argument", who); return 1; }
+  if (conv1 && conv1_desc(who, d)) return 1;
+  if (multistage_desc(who, d, levels, lv, &g) || (!conv1 && grouped_inputs(who, "network", g, x))) return 1;
+  if (ens) {
+    if (hierarchy_args(who, levels, ens->table, ens->ens_label, ens->ens_score, ens->ens_level, ens->labels, ens->confusion, &e)) return 1;
+    for (int l = 0; l < levels; ++l)
+      if (lv[l].classes != ens->table->classes[l]) {
+        dta_set_error("%s: level %d has %d classes, the hierarchy table %d", who, l, lv[l].classes, ens->table->classes[l]);
+        return 1;
+      }
+  }
+  if (conv1 ? grouped_forward_conv1(g, nets, gate, workspace, st) : grouped_forward(g, nets, x, gate, workspace, st)) return 1;
+  const SoftmaxMulti m = softmax_levels(g, levels, lv, workspace, gate, probs, top_idx, top_score);
+  return ens ? launch_softmax_top2_ensemble(m, e, st) : launch_softmax_top2_multi(m, st);
+}
+
 int dta_multistage_predict(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
                            const float* const* x, const float* gate, void* workspace, float* const* probs,
                            long long* const* top_idx, float* const* top_score, void* stream) {
-  const char* who = "dta_multistage_predict";
-  Grouped g;
-  hipStream_t st = (hipStream_t)stream;
-  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("%s: null argument", who); return 1; }
-  if (multistage_desc(who, d, levels, lv, &g) || grouped_inputs(who, "network", g, x)) return 1;
-  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
-  return launch_softmax_top2_multi(softmax_levels(g, levels, lv, workspace, gate, probs, top_idx, top_score), st);
+  return multistage_predict_impl("dta_multistage_predict", false, d, levels, lv, nets, x, gate, workspace, probs, top_idx, top_score, nullptr, stream);
+}
+int dta_conv1_multistage_predict(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
+                                 const float* gate, void* workspace, float* const* probs, long long* const* top_idx,
+                                 float* const* top_score, void* stream) {
+  return multistage_predict_impl("dta_conv1_multistage_predict", true, d, levels, lv, nets, nullptr, gate, workspace, probs, top_idx, top_score, nullptr, stream);
 }
 
 // ---- validation: eval-mode forward of every level + ONE epilogue launch (loss, softmax, top-2, metric counts) ----
@@ -1402,19 +1440,16 @@ int dta_multistage_predict_ensemble(const dta_net_desc* d, int levels, const dta
                                     long long* const* top_idx, float* const* top_score, const dta_hierarchy* table,
                                     long long* ens_label, float* ens_score, int* ens_level, const long long* labels,
                                     long long* confusion, void* stream) {
-  const char* who = "dta_multistage_predict_ensemble";
-  Grouped g; HierarchyArgs e;
-  hipStream_t st = (hipStream_t)stream;
-  if (!nets || !x || !workspace || !top_idx || !top_score) { dta_set_error("%s: null argument", who); return 1; }
-  if (multistage_desc(who, d, levels, lv, &g) || grouped_inputs(who, "network", g, x)) return 1;
-  if (hierarchy_args(who, levels, table, ens_label, ens_score, ens_level, labels, confusion, &e)) return 1;
-  for (int l = 0; l < levels; ++l)
-    if (lv[l].classes != table->classes[l]) {
-      dta_set_error("%s: level %d has %d classes, the hierarchy table %d", who, l, lv[l].classes, table->classes[l]);
-      return 1;
-    }
-  if (grouped_forward(g, nets, x, gate, workspace, st)) return 1;
-  return launch_softmax_top2_ensemble(softmax_levels(g, levels, lv, workspace, gate, probs, top_idx, top_score), e, st);
+  const EnsembleOut ens = {table, ens_label, ens_score, ens_level, labels, confusion};
+  return multistage_predict_impl("dta_multistage_predict_ensemble", false, d, levels, lv, nets, x, gate, workspace, probs, top_idx, top_score, &ens, stream);
+}
+int dta_conv1_multistage_predict_ensemble(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
+                                          const float* gate, void* workspace, float* const* probs, long long* const* top_idx,
+                                          float* const* top_score, const dta_hierarchy* table, long long* ens_label,
+                                          float* ens_score, int* ens_level, const long long* labels, long long* confusion,
+                                          void* stream) {
+  const EnsembleOut ens = {table, ens_label, ens_score, ens_level, labels, confusion};
+  return multistage_predict_impl("dta_conv1_multistage_predict_ensemble", true, d, levels, lv, nets, nullptr, gate, workspace, probs, top_idx, top_score, &ens, stream);
 }
 
 int dta_hierarchy_resolve(int levels, const long long* const* top_idx, const float* const* top_score, int batch,
@@ -1732,8 +1767,9 @@ int dta_raster_conv1_table(const dta_net_desc* d, const dta_subnet_params* nets,
   ta.raster = raster; ta.wp = scratch; ta.T = T; ta.P = (long long)height * width; ta.C = d->bands; ta.NC = g.NC; ta.N = 9 * g.cols;
   if (launch_raster_conv1_taps(ta, d->dtype == DTA_BF16, st)) return 1;
   Conv1ClassArgs ca;
-  ca.T = T; ca.bias[0] = nets[0].conv_b[0]; ca.bias[1] = G == 2 ? nets[1].conv_b[0] : nets[0].conv_b[0];
-  ca.bias_split = G == 2 ? CH[0] : g.cols; ca.A = table; ca.H = height; ca.W = width; ca.cols = g.cols; ca.fmt = g.fmt;
+  ca.T = T;
+  for (int b = 0; b < BLEND_CE_MULTI_MAX; ++b) ca.bias[b] = nets[b < G ? b : 0].conv_b[0];
+  ca.bias_split = CH[0]; ca.A = table; ca.H = height; ca.W = width; ca.cols = g.cols; ca.fmt = g.fmt;
   return launch_raster_conv1_classes(ca, st);
 }
 
@@ -1748,6 +1784,116 @@ int dta_gather_conv1_windows(const dta_net_desc* d, const void* table, int heigh
   Conv1GatherArgs a;
   a.A = table; a.origins = origins; a.out = y0; a.N = n; a.H = height; a.W = width; a.ppr = g.cols * fmt_bytes(g.fmt) / 16;
   return launch_gather_conv1_windows(a, (hipStream_t)stream);
+}
+
+// ---- ... for the levels x years of a multi-stage model: one table per year, the levels side by side ----
+namespace {
+// d: the multi-stage descriptor (DTA_NET_SPECTRAL); the table of a year has levels * 32 columns
+int multistage_conv1_geom(const char* who, const dta_net_desc* d, int levels, int height, int width, Conv1Geom* g) {
+  if (!d) { dta_set_error("%s: null argument", who); return 1; }
+  if (d->kind != DTA_NET_SPECTRAL) { dta_set_error("%s: the descriptor's kind must be DTA_NET_SPECTRAL", who); return 1; }
+  if (levels < 1 || levels > DTA_MAX_LEVELS) { dta_set_error("%s: 1..%d levels", who, DTA_MAX_LEVELS); return 1; }
+  if (conv1_geom(who, d, height, width, g)) return 1;
+  g->cols = levels * CH[0];
+  g->wp_bytes = ((size_t)g->NC * 9 * g->cols * 16 * g->esz + 255) & ~(size_t)255;
+  return 0;
+}
+}  // namespace
+
+int dta_conv1_multistage_table_bytes(const dta_net_desc* d, int levels, int height, int width, size_t* scratch_bytes,
+                                     size_t* table_bytes, size_t* mask_bytes) {
+  const char* who = "dta_conv1_multistage_table_bytes";
+  Conv1Geom g;
+  if (!scratch_bytes || !table_bytes || !mask_bytes) { dta_set_error("%s: null argument", who); return 1; }
+  if (height == 0 && width == 0) {      // a missing year: the far-outside row alone, no scratch
+    if (multistage_conv1_geom(who, d, levels, 1, 1, &g)) return 1;
+    *scratch_bytes = 0; *table_bytes = (size_t)9 * g.cols * fmt_bytes(g.fmt); *mask_bytes = 1;
+    return 0;
+  }
+  if (multistage_conv1_geom(who, d, levels, height, width, &g)) return 1;
+  *scratch_bytes = g.wp_bytes + (size_t)height * width * 9 * g.cols * 4;
+  *table_bytes = g.positions * 9 * g.cols * fmt_bytes(g.fmt);
+  *mask_bytes = g.positions;
+  return 0;
+}
+
+int dta_conv1_multistage_raster_table(const dta_net_desc* d, int levels, const dta_subnet_params* nets, const void* raster,
+                                      int height, int width, void* scratch, void* table, unsigned char* mask, void* stream) {
+  const char* who = "dta_conv1_multistage_raster_table";
+  Conv1Geom g;
+  if (!nets || !table || !mask || (raster && !scratch)) { dta_set_error("%s: null argument", who); return 1; }
+  if (multistage_conv1_geom(who, d, levels, raster ? height : 1, raster ? width : 1, &g)) return 1;
+  if (((uintptr_t)raster & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)table & 15)) { dta_set_error("%s: raster, scratch and table must be 16-byte aligned", who); return 1; }
+  for (int l = 0; l < levels; ++l)
+    if (!nets[l].conv_w[0] || !nets[l].conv_b[0]) { dta_set_error("%s: level %d: the first conv's parameters are missing", who, l); return 1; }
+  hipStream_t st = (hipStream_t)stream;
+  const bool bf16 = d->dtype == DTA_BF16;
+  Conv1ClassArgs ca;
+  ca.T = nullptr; ca.bias_split = CH[0]; ca.A = table; ca.H = height; ca.W = width; ca.cols = g.cols; ca.fmt = g.fmt;
+  for (int l = 0; l < BLEND_CE_MULTI_MAX; ++l) ca.bias[l] = nets[l < levels ? l : 0].conv_b[0];
+  if (!raster) {      // a missing year: what the first conv gives on an all-zero input, everywhere -- the biases
+    if (hipMemsetAsync(mask, 0, 1, st) != hipSuccess) { dta_set_error("%s: memset failed", who); return 1; }
+    ca.far_only = 1; ca.H = ca.W = 0;
+    return launch_raster_conv1_classes(ca, st);
+  }
+  // the levels' first-conv weights side by side along n, each as the forward packs it for its own first conv
+  PackWArgs pw;
+  memset(&pw, 0, sizeof(pw));
+  pw.G = 1; pw.NC = g.NC; pw.N = g.cols; pw.K = d->bands; pw.mode = 3; pw.nsplit = CH[0];
+  for (int l = 0; l < levels; ++l) pw.src[l] = nets[l].conv_w[0];
+  if (bf16 ? launch_pack_conv_w<bf16_t>(pw, scratch, st) : launch_pack_conv_w<float>(pw, scratch, st)) return 1;
+  float* T = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + g.wp_bytes);
+  Conv1TapsArgs ta;
+  ta.raster = raster; ta.wp = scratch; ta.T = T; ta.P = (long long)height * width; ta.C = d->bands; ta.NC = g.NC; ta.N = 9 * g.cols;
+  if (launch_raster_conv1_taps(ta, bf16, st)) return 1;
+  ca.T = T;
+  if (launch_raster_conv1_classes(ca, st)) return 1;
+  Conv1MaskArgs ma;
+  ma.raster = raster; ma.mask = mask; ma.C = d->bands; ma.NC = g.NC; ma.H = height; ma.W = width;
+  return launch_raster_conv1_mask(ma, bf16, st);
+}
+
+int dta_conv1_multistage_output_range(const dta_net_desc* d, int levels, const dta_level* lv, size_t* offset,
+                                      size_t* group_stride, size_t* bytes) {
+  const char* who = "dta_conv1_multistage_output_range";
+  Grouped g;
+  if (!offset || !group_stride || !bytes) { dta_set_error("%s: null argument", who); return 1; }
+  if (multistage_desc(who, d, levels, lv, &g)) return 1;
+  *offset = g.p.y[0];
+  *group_stride = (size_t)g.p.B * g.p.HWc[0] * CH[0] * fmt_bytes(g.p.y_fmt);
+  *bytes = *group_stride * g.p.G;
+  return 0;
+}
+
+int dta_conv1_multistage_gather_windows(const dta_net_desc* d, int levels, const dta_level* lv, int years,
+                                        const void* const* tables, const unsigned char* const* masks, const int* present,
+                                        int height, int width, const int* origins, int n, void* workspace, float* flags,
+                                        float* clear_next, void* stream) {
+  const char* who = "dta_conv1_multistage_gather_windows";
+  Grouped g; Conv1Geom cg;
+  if (!tables || !masks || !present || !origins || !workspace || !flags || flags == clear_next) { dta_set_error("%s: null argument (or flags == clear_next)", who); return 1; }
+  if (conv1_desc(who, d) || multistage_desc(who, d, levels, lv, &g) || multistage_conv1_geom(who, d, levels, height, width, &cg)) return 1;
+  if (years < 1 || years > DTA_MAX_YEARS) { dta_set_error("%s: 1..%d years, not %d", who, DTA_MAX_YEARS, years); return 1; }
+  for (int l = 0; l < levels; ++l)
+    if (lv[l].count != years) { dta_set_error("%s: level %d has %d networks, the call %d years", who, l, lv[l].count, years); return 1; }
+  if (n < 1 || n > d->batch) { dta_set_error("%s: bad shape: n=%d (the descriptor's batch is %d)", who, n, d->batch); return 1; }
+  Conv1GatherYearsArgs a;
+  memset(&a, 0, sizeof(a));
+  int have = 0;
+  for (int y = 0; y < years; ++y) {
+    if (!tables[y] || !masks[y]) { dta_set_error("%s: year %d: null table or mask (a missing year has the far-outside row and one zero byte)", who, y); return 1; }
+    if ((uintptr_t)tables[y] & 15) { dta_set_error("%s: year %d: the table must be 16-byte aligned", who, y); return 1; }
+    a.A[y] = tables[y]; a.mask[y] = masks[y]; a.whole[y] = present[y] != 0;
+    have += a.whole[y];
+  }
+  if (!have) { dta_set_error("%s: every year is missing: nothing to gather", who); return 1; }
+  if ((uintptr_t)workspace & 15) { dta_set_error("%s: the workspace must be 16-byte aligned", who); return 1; }
+  for (int l = 0; l < levels; ++l) a.first[l] = lv[l].first;
+  a.origins = origins; a.out = at<char>(workspace, g.p.y[0]);
+  a.group_bytes = (size_t)g.p.B * g.p.HWc[0] * CH[0] * fmt_bytes(g.p.y_fmt);
+  a.N = n; a.H = height; a.W = width; a.levels = levels; a.ppl = CH[0] * fmt_bytes(cg.fmt) / 16; a.years = years;
+  a.flags = flags; a.clear_next = clear_next;
+  return launch_gather_conv1_windows_years(a, (hipStream_t)stream);
 }
 
 int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns, int classes, float* mean,

@@ -108,6 +108,7 @@ template int launch_pack_input<bf16_t>(const float*, void*, int, int, int, int, 
 //   mode 0: forward, one source per group                 val = W_g[n][kc][tap]
 //   mode 1: forward, G==1, output columns concatenated     val = (n<nsplit ? W_0[n] : W_1[n-nsplit])[kc][tap]
 //   mode 2: input-gradient form (transposed + flipped)     val = W_g[kc][n][8-tap]   (W_g is [Kdim][N][9])
+//   mode 3: forward, G==1, any number of sources side by side   val = W_{n / nsplit}[n % nsplit][kc][tap]
 // ------------------------------------------------------------------------------------------------
 // (an item is one 16-wide row of the image -- (group, chunk, tap, n) decoded ONCE with 32-bit arithmetic, its sixteen values
 //  gathered with all loads in flight and written as one contiguous 32- / 64-byte run; the element-per-thread form decoded every
@@ -127,6 +128,7 @@ __device__ __forceinline__ void pack_conv_w_job(const PackWArgs& a, T* __restric
     size_t base, kstride;      // value of contraction channel kc: w[base + kc * kstride]
     if (a.mode == 0) { w = a.src[g]; base = (size_t)n * a.K * 9 + tap; kstride = 9; }
     else if (a.mode == 1) { w = n < a.nsplit ? a.src[0] : a.src[1]; base = (size_t)(n < a.nsplit ? n : n - a.nsplit) * a.K * 9 + tap; kstride = 9; }
+    else if (a.mode == 3) { w = a.src[n / a.nsplit]; base = (size_t)(n % a.nsplit) * a.K * 9 + tap; kstride = 9; }
     else { w = a.src[g]; base = (size_t)n * 9 + (8 - tap); kstride = (size_t)N * 9; }
     float v[16];
 #pragma unroll

@@ -10,6 +10,15 @@
 // launch_conv3x3 writes into the forward's y[0] (pre-BatchNorm, bias included, the plan's y_fmt), so the forward that
 // follows the gather skips its first conv and nothing downstream changes.  dense.conv1_table_np / gather_conv1_np are
 // the written-down meaning.  No atomics, one float32 accumulator per element, fixed orders: reruns are bit-identical.
+// For a multi-stage model (levels x years spectral networks; every level's year-y network reads year y's raster) the
+// table of a year holds the levels side by side -- columns 32 l .. 32 l + 31 are level l's year-y first conv -- so a
+// raster is read ONCE for all levels:
+//   k_raster_conv1_mask           mask[p] = the raster pixel under table position p has a non-zero stored element
+//   k_gather_conv1_windows_years  the gather for all levels x years in one launch (blockIdx.y = year), each level's 32
+//                                 columns into its (level, year) group's y[0]; sets the years' 0/1 flags from the mask
+// Sizes per raster pixel and year: 9 x 32 x levels x 2 B of table in half (4 B in fp32) and 9 x 32 x levels x 4 B of T in
+// the scratch, which the years share (they are built one after the other).  5 levels at 256x256: 189 MB of table per year
+// plus 377 MB of shared scratch.
 #include "kernels.h"
 
 namespace dta {
@@ -111,11 +120,11 @@ __global__ __launch_bounds__(256) void k_raster_conv1_taps(Conv1TapsArgs a) {
 __global__ __launch_bounds__(256) void k_raster_conv1_classes(Conv1ClassArgs a) {
   const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
   const int cols = a.cols, W2 = a.W + 2;
-  const size_t far = (size_t)(a.H + 2) * W2;
+  const size_t far = a.far_only ? 0 : (size_t)(a.H + 2) * W2;
   if (id >= (far + 1) * cols) return;
   const int n = (int)(id % cols);
   const size_t pos = id / cols;
-  const float b = n < a.bias_split ? a.bias[0][n] : a.bias[1][n - a.bias_split];
+  const float b = a.bias[n / a.bias_split][n % a.bias_split];
   float t[3][3];
 #pragma unroll
   for (int u = 0; u < 3; ++u)
@@ -167,6 +176,68 @@ __global__ __launch_bounds__(256) void k_gather_conv1_windows(Conv1GatherArgs a)
   reinterpret_cast<u32x4*>(a.out)[id] = reinterpret_cast<const u32x4*>(a.A)[((size_t)pos * 9 + cls) * ppr + piece];
 }
 
+// One lane per table position, lanes along the positions: a wave reads runs of consecutive pixels (a float32 plane: 4 B
+// per lane and band; a bf16 chunk: the pixel's 32 B) and writes 64 consecutive bytes.  The ring and the far-outside row
+// are 0.  bf16 chunks hold zeros in the bands past C, so whole chunks are tested; -0 is zero, NaN is not.
+template <typename T>
+__global__ __launch_bounds__(256) void k_raster_conv1_mask(Conv1MaskArgs a) {
+  const size_t pos = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int W2 = a.W + 2;
+  const size_t far = (size_t)(a.H + 2) * W2;
+  if (pos > far) return;
+  bool hit = false;
+  const int r = (int)(pos / W2) - 1, c = (int)(pos % W2) - 1;
+  if (pos < far && r >= 0 && r < a.H && c >= 0 && c < a.W) {
+    const size_t P = (size_t)a.H * a.W, p = (size_t)r * a.W + c;
+    if constexpr (sizeof(T) == 2) {
+      const u32x4* ras = reinterpret_cast<const u32x4*>(a.raster);
+      for (int ch = 0; ch < a.NC; ++ch)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const u32x4 v = ras[((size_t)ch * P + p) * 2 + half];
+          hit |= ((v[0] | v[1] | v[2] | v[3]) & 0x7FFF7FFFu) != 0u;
+        }
+    } else {
+      const float* ras = reinterpret_cast<const float*>(a.raster);
+      for (int k = 0; k < a.C; ++k) hit |= !(ras[(size_t)k * P + p] == 0.f);
+    }
+  }
+  a.mask[pos] = hit ? 1 : 0;
+}
+
+// k_gather_conv1_windows for every (level, year) group of a multi-stage model: blockIdx.y = year, a lane copies one
+// 16-byte piece of one output row; consecutive lanes take consecutive pieces of the year's table row (levels * ppl of
+// them: a wave's loads are whole table rows), level l's ppl pieces land in group first[l] + year at row stride ppl pieces.
+// Position, class and far-outside rules as above; a year with whole == 0 reads its one far-outside row everywhere.
+// Flags: dta_gather_windows_years' protocol -- a wave that saw a set mask byte stores 1.f once (plain stores of one
+// value: no atomics, any order); flags arrive zeroed, block 0 of each year zeroes clear_next.
+__global__ __launch_bounds__(256) void k_gather_conv1_windows_years(Conv1GatherYearsArgs a) {
+  const int y = blockIdx.y;
+  if (a.clear_next && blockIdx.x == 0 && threadIdx.x == 0) a.clear_next[y] = 0.f;
+  const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int ppl = a.ppl, ppr = a.levels * ppl;
+  bool hit = false;
+  if (id < (size_t)a.N * 121 * ppr) {
+    const int piece = (int)(id % ppr);
+    const size_t row = id / ppr;
+    const int n = (int)(row / 121), r = (int)(row - (size_t)n * 121);
+    const int i = r / 11, j = r - i * 11;
+    long long pos = 0;
+    if (a.whole[y]) {
+      const long long rr = (long long)a.origins[2 * n] + i, cc = (long long)a.origins[2 * n + 1] + j;
+      const long long W2 = (long long)a.W + 2;
+      pos = ((long long)a.H + 2) * W2;      // far outside
+      if (rr >= -1 && rr <= a.H && cc >= -1 && cc <= a.W) pos = (rr + 1) * W2 + (cc + 1);
+    }
+    const int cls = (i == 0 ? 0 : (i == 10 ? 2 : 1)) * 3 + (j == 0 ? 0 : (j == 10 ? 2 : 1));
+    const int l = piece / ppl, q = piece - l * ppl;
+    char* dst = reinterpret_cast<char*>(a.out) + (size_t)(a.first[l] + y) * a.group_bytes;
+    reinterpret_cast<u32x4*>(dst)[row * ppl + q] = reinterpret_cast<const u32x4*>(a.A[y])[((size_t)pos * 9 + cls) * ppr + piece];
+    hit = a.mask[y][pos] != 0;
+  }
+  if (__any(hit) && (threadIdx.x & 63) == 0) a.flags[y] = 1.f;
+}
+
 }  // namespace
 
 int launch_raster_conv1_taps(const Conv1TapsArgs& a, bool bf16, hipStream_t st) {
@@ -181,7 +252,7 @@ int launch_raster_conv1_taps(const Conv1TapsArgs& a, bool bf16, hipStream_t st) 
 }
 
 int launch_raster_conv1_classes(const Conv1ClassArgs& a, hipStream_t st) {
-  const size_t total = ((size_t)(a.H + 2) * (a.W + 2) + 1) * a.cols, blocks = (total + 255) / 256;
+  const size_t total = (a.far_only ? 1 : (size_t)(a.H + 2) * (a.W + 2) + 1) * a.cols, blocks = (total + 255) / 256;
   if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_raster_conv1_table: raster too large for one launch"); return 1; }
   hipLaunchKernelGGL(k_raster_conv1_classes, dim3((unsigned)blocks), dim3(256), 0, st, a);
   DTA_CHECK_LAUNCH("k_raster_conv1_classes");
@@ -193,6 +264,25 @@ int launch_gather_conv1_windows(const Conv1GatherArgs& a, hipStream_t st) {
   if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_conv1_windows: batch too large for one launch"); return 1; }
   hipLaunchKernelGGL(k_gather_conv1_windows, dim3((unsigned)blocks), dim3(256), 0, st, a);
   DTA_CHECK_LAUNCH("k_gather_conv1_windows");
+  return 0;
+}
+
+int launch_raster_conv1_mask(const Conv1MaskArgs& a, bool bf16, hipStream_t st) {
+  const size_t total = (size_t)(a.H + 2) * (a.W + 2) + 1, blocks = (total + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_conv1_multistage_raster_table: raster too large for one launch"); return 1; }
+  if (bf16) hipLaunchKernelGGL(k_raster_conv1_mask<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_raster_conv1_mask<float>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_raster_conv1_mask");
+  return 0;
+}
+
+int launch_gather_conv1_windows_years(const Conv1GatherYearsArgs& a, hipStream_t st) {
+  const size_t total = (size_t)a.N * 121 * a.levels * a.ppl, blocks = (total + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_conv1_multistage_gather_windows: batch too large for one launch"); return 1; }
+  // flags must be zero on entry: cleared here, unless the caller alternates two banks and lets each call clear the other
+  if (!a.clear_next && hipMemsetAsync(a.flags, 0, sizeof(float) * a.years, st) != hipSuccess) { dta_set_error("dta_conv1_multistage_gather_windows: memset failed"); return 1; }
+  hipLaunchKernelGGL(k_gather_conv1_windows_years, dim3((unsigned)blocks, a.years), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_gather_conv1_windows_years");
   return 0;
 }
 

@@ -710,11 +710,24 @@ int launch_crown_resolve(const CrownResolveArgs& a, hipStream_t st);
 struct Conv1TapsArgs { const void* raster; const void* wp; float* T; long long P; int C, NC, N; };
 int launch_raster_conv1_taps(const Conv1TapsArgs& a, bool bf16, hipStream_t st);
 // A [(H + 2) * (W + 2) + 1][9][cols] in `fmt`: the nine class sums of every position of the raster with its ring, then the
-// far-outside row; bias of column n: bias[0][n] below bias_split, else bias[1][n - bias_split]
-struct Conv1ClassArgs { const float* T; const float* bias[2]; int bias_split; void* A; int H, W, cols, fmt; };
+// far-outside row; bias of column n: bias[n / bias_split][n % bias_split] (Hang2020's two branches, or the levels of a
+// multi-stage model side by side).  far_only: the table is the far-outside row alone (a missing year; T is not read)
+struct Conv1ClassArgs { const float* T; const float* bias[BLEND_CE_MULTI_MAX]; int bias_split; void* A; int H, W, cols, fmt; int far_only = 0; };
 int launch_raster_conv1_classes(const Conv1ClassArgs& a, hipStream_t st);
 // rows [N * 121] of ppr 16-byte pieces each, copied out of A (same piece count per class row)
 struct Conv1GatherArgs { const void* A; const int* origins; void* out; int N, H, W, ppr; };
 int launch_gather_conv1_windows(const Conv1GatherArgs& a, hipStream_t st);
+// mask [(H + 2) * (W + 2) + 1] bytes: 1 where the raster pixel under a table position has a non-zero stored element (NaN
+// counts), 0 on the ring and in the far-outside row; raster in the form of Conv1TapsArgs (bf16: chunks, float32: planes)
+struct Conv1MaskArgs { const void* raster; unsigned char* mask; int C, NC, H, W; };
+int launch_raster_conv1_mask(const Conv1MaskArgs& a, bool bf16, hipStream_t st);
+// The levels x years form (blockIdx.y = year): year y's table A[y] has levels * ppl pieces per class row, level l's ppl
+// pieces of output row r go to out + (first[l] + y) * group_bytes + (r * ppl + piece) * 16.  whole[y] == 0: the table is the
+// far-outside row alone and the mask one zero byte (a missing year).  flags / clear_next: GatherYearsArgs' protocol, a
+// year's flag set when any position of the batch's windows has its mask byte set
+struct Conv1GatherYearsArgs { const void* A[MAXG]; const unsigned char* mask[MAXG]; int whole[MAXG]; int first[BLEND_CE_MULTI_MAX];
+                              const int* origins; void* out; size_t group_bytes; int N, H, W, levels, ppl, years;
+                              float* flags; float* clear_next; };
+int launch_gather_conv1_windows_years(const Conv1GatherYearsArgs& a, hipStream_t st);
 
 }  // namespace dta

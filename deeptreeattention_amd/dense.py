@@ -43,8 +43,19 @@ window position depends only on the raster pixel underneath and on which taps fa
     Conv1Table.gather            origins -> the first conv's output of a batch, written into the Predictor's workspace
                                  (dta_gather_conv1_windows); the forward then starts behind its first conv (dta_conv1_forward)
 
+predict_windows_multistage / predict_map_multistage take share_conv1=True too (opt-in; the rasters in the MODELS'
+precision): every level's year-y network reads year y's raster, so a year's first convs of ALL levels are one table --
+
+    Conv1TableYears              per year: raster + the levels' year-y first convs side by side -> one table and the raster's
+                                 non-zero mask (dta_conv1_multistage_raster_table), once per call; a missing year: the biases
+    Conv1TableYears.gather       origins -> the first convs of a batch for every level x year, written into the
+                                 MultiStagePredictor's workspace in ONE launch that also sets the years' flags
+                                 (dta_conv1_multistage_gather_windows); the grouped forward then starts behind its first
+                                 convs (dta_conv1_multistage_predict_ensemble)
+
 `gather_windows_np`, `crown_reduce_np` and `crown_resolve_np` are the written-down meaning of the gather, reduce and
-resolve kernels, `conv1_table_np` and `gather_conv1_np` that of the first-conv table and its gather.
+resolve kernels, `conv1_table_np` and `gather_conv1_np` that of the first-conv table and its gather, `conv1_mask_np`,
+`gather_conv1_years_np` and `year_flags_np` that of the multi-stage form.
 File reading and georeferencing stay with the caller, as in preprocess.py."""
 import collections
 
@@ -147,6 +158,64 @@ def gather_conv1_np(table, origins, size=WINDOW):
                 pos = (rr + 1) * (Ww + 2) + (cc + 1) if -1 <= rr <= Hh and -1 <= cc <= Ww else far
                 out[n, i * size + j] = data[pos, conv1_class(i, size) * 3 + conv1_class(j, size)]
     return out
+
+
+def conv1_mask_np(raster_norm):
+    """The non-zero mask dta_conv1_multistage_raster_table writes next to a year's table: uint8 [(H + 2) * (W + 2) + 1], one
+    byte per table position -- 1 where the raster pixel under it has a non-zero stored element (NaN counts as non-zero),
+    0 on the ring and in the far-outside row.  raster_norm [C][H][W] as stored (a bf16 raster: its bf16 values);
+    None (a missing year): the single zero byte."""
+    if raster_norm is None:
+        return np.zeros(1, dtype=np.uint8)
+    x = np.asarray(raster_norm)
+    Cb, Hh, Ww = x.shape
+    grid = np.zeros((Hh + 2, Ww + 2), dtype=np.uint8)
+    grid[1:-1, 1:-1] = (~(x == 0)).any(axis=0)
+    return np.concatenate([grid.reshape(-1), np.zeros(1, dtype=np.uint8)])
+
+
+def gather_conv1_years_np(tables, origins, levels, size=WINDOW):
+    """What dta_conv1_multistage_gather_windows writes.  tables: one Conv1TableNP per year with data
+    [(H + 2) * (W + 2) + 1][9][levels * cols] (the levels side by side); a missing year's data is the far-outside row alone,
+    [1][9][levels * cols], and every position reads it.  Returns [levels][years][N][size * size][cols]: slice (l, y) is
+    gather_conv1_np on columns cols * l .. cols * l + cols - 1 of year y's table -- the first conv of level l's year-y network,
+    group l * years + y of the multi-stage forward.  A pure copy: the table's dtype and bits."""
+    origins = np.asarray(origins).reshape(-1, 2)
+    width = tables[0].data.shape[2]
+    if width % levels:
+        raise ValueError("{} table columns do not divide into {} levels".format(width, levels))
+    cols = width // levels
+    out = np.empty((levels, len(tables), len(origins), size * size, cols), dtype=tables[0].data.dtype)
+    for y, t in enumerate(tables):
+        if t.data.shape[0] == 1:        # a missing year: class by class the one row
+            cls = [conv1_class(i, size) * 3 + conv1_class(j, size) for i in range(size) for j in range(size)]
+            full = np.broadcast_to(t.data[0][cls], (len(origins), size * size, width))
+        else:
+            full = gather_conv1_np(t, origins, size)
+        for l in range(levels):
+            out[l, y] = full[:, :, l * cols:(l + 1) * cols]
+    return out
+
+
+def year_flags_np(rasters_norm, origins, size=WINDOW):
+    """The years' flags dta_conv1_multistage_gather_windows sets: float32 [years], 1 where any position of any window lies
+    on a raster pixel with a non-zero stored element (NaN counts), else 0 -- a missing year (None) and an all-zero raster
+    give 0, as do windows that miss the raster.  rasters_norm: per year [C][H][W] as stored, or None.  For float32 rasters
+    this is what dta_year_flags says about the gathered float32 batches."""
+    origins = np.asarray(origins).reshape(-1, 2)
+    flags = np.zeros(len(rasters_norm), dtype=np.float32)
+    for y, x in enumerate(rasters_norm):
+        if x is None:
+            continue
+        Hh, Ww = np.asarray(x).shape[1:]
+        mask = conv1_mask_np(x)[:-1].reshape(Hh + 2, Ww + 2)[1:-1, 1:-1]
+        for r, c in origins:
+            r, c = int(r), int(c)
+            ra, rb, ca, cb = max(r, 0), min(r + size, Hh), max(c, 0), min(c + size, Ww)
+            if ra < rb and ca < cb and mask[ra:rb, ca:cb].any():
+                flags[y] = 1.0
+                break
+    return flags
 
 
 def crown_reduce_np(probs, offsets):
@@ -384,6 +453,105 @@ class Conv1Table:
         return Conv1TableNP(self.data.cpu().numpy(), self.height, self.width)
 
 
+def _share_conv1_multistage_models(predictor, size):
+    """The model side of _share_conv1_multistage_refusals.  Returns the networks."""
+    mods = [m for p in predictor.preds for m in p.nets_mod]
+    if any(m.training for m in mods):
+        raise RuntimeError("share_conv1: a network is in training mode; prediction runs eval-mode BatchNorm (model.eval())")
+    if any(m.precision != mods[0].precision for m in mods):
+        raise RuntimeError("share_conv1: all levels must run in the same precision")
+    if size != 11:
+        raise RuntimeError("share_conv1: window side {} -- the first-conv table is laid out for 11x11 windows only".format(size))
+    return mods
+
+
+def _share_conv1_multistage_refusals(predictor, rs, size):
+    """What the shared first conv of the multi-stage route does not cover, after _multistage_years; raises before anything
+    is allocated or launched.  Returns the present years' rasters."""
+    mods = _share_conv1_multistage_models(predictor, size)
+    m0 = mods[0]
+    have = [r for r in rs if r is not None]
+    if not have:
+        raise ValueError("at least one year's raster must be present")
+    for r in have:
+        if not isinstance(r, DenseRaster):
+            raise TypeError("rasters must be DenseRaster objects")
+        if r.precision != m0.precision:
+            raise RuntimeError("share_conv1: {}-mode networks need DenseRaster(..., precision={!r}), not {!r}"
+                               .format(m0.precision, m0.precision, r.precision))
+        if r.shape != have[0].shape or r.device != have[0].device:
+            raise ValueError("all years' rasters must share one shape and device")
+    for m in mods:
+        w = next(t for t in m.parameters() if t.dim() == 4)
+        if w.shape[1] != have[0].bands:
+            raise RuntimeError("share_conv1: the networks take {} bands, the normalised rasters have {}".format(w.shape[1], have[0].bands))
+    return have
+
+
+class Conv1TableYears:
+    """The first convs of a multi-stage model's levels x years networks for every position a window can put over the
+    years' rasters (module text; csrc/dense_conv1.hip): per year one table [(H + 2) * (W + 2) + 1][9][levels * 32] -- columns
+    32 l .. 32 l + 31 level l's year-y network -- in the storage Conv1Table uses, and the raster's non-zero mask, one byte
+    per position.  A missing year (None): the far-outside row alone, [1][9][levels * 32], and one zero byte.  The years are
+    built one after the other through ONE scratch.  Built from the networks' weights at construction."""
+
+    def __init__(self, rasters, predictor):
+        L = _lib.lib()
+        rs = list(rasters)
+        r0 = next(r for r in rs if r is not None)
+        m0 = predictor.preds[0].nets_mod[0]
+        self.height, self.width, self.bands, self.precision, self.device = r0.height, r0.width, r0.bands, r0.precision, r0.device
+        self.levels, self.years = len(predictor.preds), len(rs)
+        self.cols = 32 * self.levels
+        self.present = [r is not None for r in rs]
+        from . import Hang2020 as H
+        self.desc = _lib.NetDesc(1, r0.bands, WINDOW, WINDOW, m0._classes, _lib.NET_SPECTRAL, _lib.dtype_code(m0.precision), 0,
+                                 4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
+        dt = torch.float16 if self.precision == "bf16" else torch.float32
+        size_t = _lib.C.c_size_t
+
+        def sizes(h, w):
+            sb, tb, mb = size_t(), size_t(), size_t()
+            _lib.check(L.dta_conv1_multistage_table_bytes(_lib.C.byref(self.desc), self.levels, h, w, _lib.C.byref(sb), _lib.C.byref(tb),
+                                                          _lib.C.byref(mb)), "dta_conv1_multistage_table_bytes")
+            return sb.value, tb.value, mb.value
+        scratch_b, table_b, mask_b = sizes(self.height, self.width)
+        _, far_b, _ = sizes(0, 0)
+        positions = (self.height + 2) * (self.width + 2) + 1
+        if table_b != positions * 9 * self.cols * dt.itemsize or mask_b != positions or far_b != 9 * self.cols * dt.itemsize:
+            raise RuntimeError("dta_conv1_multistage_table_bytes: {} / {} / {} bytes are not what the binding expects".format(table_b, mask_b, far_b))
+        scratch = torch.empty(scratch_b, dtype=torch.uint8, device=self.device)      # T and the weight image: shared by the years
+        self.data, self.mask = [], []
+        st = _lib.current_stream_ptr()
+        for y, r in enumerate(rs):
+            n = positions if r is not None else 1
+            self.data.append(torch.empty(n, 9, self.cols, dtype=dt, device=self.device))
+            self.mask.append(torch.empty(n, dtype=torch.uint8, device=self.device))
+            nets = (_lib.SubnetParams * self.levels)(*[p._tables([p.nets_mod[y]])[0][0] for p in predictor.preds])
+            _lib.check(L.dta_conv1_multistage_raster_table(_lib.C.byref(self.desc), self.levels, nets, _lib.ptr(r.data) if r is not None else None,
+                                                           self.height, self.width, _lib.ptr(scratch), _lib.ptr(self.data[y]),
+                                                           _lib.ptr(self.mask[y]), st), "dta_conv1_multistage_raster_table")
+        self._tp = (_lib.C.c_void_p * self.years)(*[t.data_ptr() for t in self.data])
+        self._mp = (_lib.C.c_void_p * self.years)(*[t.data_ptr() for t in self.mask])
+        self._pr = (_lib.C.c_int * self.years)(*[int(p) for p in self.present])
+
+    def gather(self, origins, predictor, flags, clear_next):
+        """origins: device int32 [n][2].  Fills predictor.conv1_slot(n, bands) -- every (level, year) group's first conv --
+        and sets flags (float32 [years]; dta_gather_windows_years' banks: `flags` zero on entry, `clear_next` zeroed by this
+        call, or None: flags cleared first).  Returns flags."""
+        n = origins.shape[0]
+        predictor._prepare_conv1(n, self.bands)
+        _lib.check(_lib.lib().dta_conv1_multistage_gather_windows(
+            _lib.C.byref(predictor.desc), self.levels, predictor.lv, self.years, self._tp, self._mp, self._pr, self.height, self.width,
+            _lib.ptr(origins), n, _lib.ptr(predictor.ws), _lib.ptr(flags), _lib.ptr(clear_next), _lib.current_stream_ptr()),
+            "dta_conv1_multistage_gather_windows")
+        return flags
+
+    def numpy(self):
+        """The years' tables read back, in the form gather_conv1_years_np takes."""
+        return [Conv1TableNP(t.cpu().numpy(), self.height, self.width) for t in self.data]
+
+
 def _check_years(rs):
     """The years' rasters of a multi-stage / float32 ensemble route: fp32 DenseRasters of one shape, None = missing, at
     least one present.  Returns the present ones.  Launches nothing."""
@@ -614,7 +782,8 @@ def _multistage_years(predictor, rasters):
     return rs
 
 
-def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False):
+def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False,
+                               share_conv1=False):
     """Per-window species prediction of a multi-stage model on 11x11 windows: walks `origins` in batches of `batch_size` --
     ONE gather launch for all years (dta_gather_windows_years, which also decides the years' flags), then the levels x years
     forward, every level's softmax / top-2 and the hierarchy walk as MultiStagePredictor.ensemble(year_flags=...) runs them
@@ -625,10 +794,16 @@ def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, 
     crown_offsets ([n + 1], windows grouped by crown as window_origins returns them): also one species per crown
     (crown_resolve: per level the mean over the crown's windows, then the walk -- this package's definition, see the
     module text) with the crown's window votes.
+    share_conv1=True (networks in eval mode; the rasters in the MODELS' precision -- DenseRaster(..., precision="bf16") for
+    bf16-mode networks): every year's raster goes through the first convs of all levels ONCE (Conv1TableYears, built in this
+    call: weight updates between calls are followed), each batch is ONE gather launch of their outputs into the predictor's
+    workspace -- which also sets the years' flags from the rasters' non-zero masks -- and the grouped forward without its
+    first convs; no window of the input is ever formed.  What it does not cover raises RuntimeError before anything is
+    allocated (_share_conv1_multistage_refusals).
     Returns MultiStageWindowPredictions(ens_label int64 [N], ens_score float32 [N], ens_level int32 [N], top_idx / top_score:
     one [N, 2] tensor per level, probs: one [N, classes_l] tensor per level or None, crowns: CrownSpecies or None)."""
     rs = _multistage_years(predictor, rasters)
-    have = _check_years(rs)
+    have = _share_conv1_multistage_refusals(predictor, rs, WINDOW) if share_conv1 else _check_years(rs)
     r0 = have[0]
     dev, size, Y = r0.device, WINDOW, len(rs)
     o = r0._origins(origins)
@@ -646,18 +821,26 @@ def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, 
     B = min(int(batch_size), N)
     if B < 1:
         raise ValueError("batch_size must be positive")
-    zeros = None
-    if len(have) < Y:      # ONE persistent zero batch stands in for every missing year
-        zeros = torch.zeros(B, r0.bands, size, size, dtype=torch.float32, device=dev)
-    bufs = [zeros if r is None else torch.empty(B, r0.bands, size, size, dtype=torch.float32, device=dev) for r in rs]
+    if share_conv1:
+        table = Conv1TableYears(rs, predictor)
+    else:
+        zeros = None
+        if len(have) < Y:      # ONE persistent zero batch stands in for every missing year
+            zeros = torch.zeros(B, r0.bands, size, size, dtype=torch.float32, device=dev)
+        bufs = [zeros if r is None else torch.empty(B, r0.bands, size, size, dtype=torch.float32, device=dev) for r in rs]
     banks = [torch.zeros(Y, dtype=torch.float32, device=dev) for _ in range(2)]
     bank = 0
     for n0 in range(0, N, B):
         n = min(B, N - n0)
-        xs = [b[:n] for b in bufs]
-        flags = DenseRaster.windows_years(rs, o[n0:n0 + n], xs, banks[bank], banks[bank ^ 1], size=size)
-        bank ^= 1
-        e = predictor.ensemble(xs, year_flags=flags, return_probs=keep)
+        if share_conv1:
+            flags = table.gather(o[n0:n0 + n], predictor, banks[bank], banks[bank ^ 1])
+            bank ^= 1
+            e = predictor.ensemble_from_conv1(flags, return_probs=keep)
+        else:
+            xs = [b[:n] for b in bufs]
+            flags = DenseRaster.windows_years(rs, o[n0:n0 + n], xs, banks[bank], banks[bank ^ 1], size=size)
+            bank ^= 1
+            e = predictor.ensemble(xs, year_flags=flags, return_probs=keep)
         for dst, src in zip(ens, e):
             dst[n0:n0 + n].copy_(src)
         for l in range(nl):
@@ -671,21 +854,28 @@ def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, 
     return MultiStageWindowPredictions(ens[0], ens[1], ens[2], top_idx, top_score, probs if return_probs else None, crowns)
 
 
-def predict_map_multistage(predictor, rasters, anchor="center", rows=None, cols=None, clip=10, batch_size=4096):
+def predict_map_multistage(predictor, rasters, anchor="center", rows=None, cols=None, clip=10, batch_size=4096, share_conv1=False):
     """A species map of a raster region from a multi-stage model: rows / cols are half-open (start, stop) pixel ranges
     (default: the whole raster).  rasters: per year a raw band-first array or a DenseRaster(..., precision="fp32"), None for
-    a missing year.  Returns (species [h][w] int64, score [h][w] float32, level [h][w] int32): each pixel's window's
+    a missing year.  share_conv1: as for predict_windows_multistage (raw arrays are made resident in the models' precision).
+    Returns (species [h][w] int64, score [h][w] float32, level [h][w] int32): each pixel's window's
     ens_label, the top-1 probability of the level that decided, and that level."""
     rs = _multistage_years(predictor, rasters)
     if all(r is None for r in rs):
         raise ValueError("at least one year's raster must be present")
-    rs = [r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision="fp32", device=predictor.device)
+    want = "fp32"
+    if share_conv1:      # every refusal before a raw array is made resident
+        want = _share_conv1_multistage_models(predictor, WINDOW)[0].precision
+        resident = [r for r in rs if isinstance(r, DenseRaster)]
+        if resident:
+            _share_conv1_multistage_refusals(predictor, resident, WINDOW)
+    rs = [r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision=want, device=predictor.device)
           for r in rs]
-    first = _check_years(rs)[0]
+    first = (_share_conv1_multistage_refusals(predictor, rs, WINDOW) if share_conv1 else _check_years(rs))[0]
     r0, r1 = rows if rows is not None else (0, first.height)
     c0, c1 = cols if cols is not None else (0, first.width)
     origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
-    res = predict_windows_multistage(predictor, rs, origins, batch_size=batch_size)
+    res = predict_windows_multistage(predictor, rs, origins, batch_size=batch_size, share_conv1=share_conv1)
     h, w = r1 - r0, c1 - c0
     return res.ens_label.reshape(h, w), res.ens_score.reshape(h, w), res.ens_level.reshape(h, w)
 

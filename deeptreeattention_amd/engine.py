@@ -2276,11 +2276,14 @@ class MultiStagePredictor:
     then softmax + top-2 per level (dta_softmax_top2).  Tile prediction is the reference's largest wall-clock consumer
     (SLURM/predict.sh), at `predict_batch_size: 64` -- where one chain per level is pure launch-latency floor.
     models: the levels' learned_ensembles (same year count, bands and precision).  Missing years are decided on the device
-    unless `present` (one list of booleans, shared by the levels: they see the same crops) is passed."""
+    unless `present` (one list of booleans, shared by the levels: they see the same crops) is passed.
+    conv1_slot / from_conv1 / ensemble_from_conv1: the same chain behind first convs that are already in the workspace
+    (dense.predict_windows_multistage(share_conv1=True): one table per year raster, one gather launch per batch)."""
 
     def __init__(self, models, frozen=False, hierarchy=None):
         self.frozen = bool(frozen)      # as Predictor: keep the weight re-layouts of the first call (refresh() after updates)
         self._packed = False
+        self._packed_conv1 = False
         self.preds = [Predictor(m) for m in models]
         if not all(p.ensemble for p in self.preds):
             raise TypeError("MultiStagePredictor needs year.learned_ensemble levels")
@@ -2316,6 +2319,7 @@ class MultiStagePredictor:
         self.desc_reuse = _lib.NetDesc(B, bands, Hh, Ww, m0._classes, _lib.NET_SPECTRAL, _lib.dtype_code(m0.precision), 0,
                                        4 | _lib.FORWARD_ONLY | _lib.REUSE_PACKED, H.BN_MOMENTUM, H.BN_EPS)
         self._packed = False
+        self._packed_conv1 = False
         nets, lv = [], []
         self.logits, self.probs, self.top_idx, self.top_score = [], [], [], []
         for p, ms in zip(self.preds, mods):
@@ -2370,6 +2374,78 @@ class MultiStagePredictor:
     def per_level(self, return_probs=True):
         """The last call's (probs or None, top_idx, top_score) triple per level."""
         return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(len(self.preds))]
+
+    def _prepare_conv1(self, n, bands):
+        """The workspace for a batch of n 11x11 windows with every year kept.  Returns the year count."""
+        years = len(self.preds[0].nets_mod)
+        self._prepare((int(n), int(bands), 11, 11), list(range(years)))
+        return years
+
+    def conv1_slot(self, n, bands):
+        """The place of the first convs' outputs inside this predictor's workspace for a batch of n 11x11 windows (the
+        workspace is (re)built for that batch shape, every year kept): a uint8 view [levels * years][group bytes], row
+        l * years + y the [n * 121][32] output of level l's year-y network, for dta_conv1_multistage_gather_windows to fill
+        (dense.Conv1TableYears.gather)."""
+        years = self._prepare_conv1(n, bands)
+        off, stride, nbytes = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.lib().dta_conv1_multistage_output_range(C.byref(self.desc), len(self.lv), self.lv, C.byref(off), C.byref(stride),
+                                                                C.byref(nbytes)), "dta_conv1_multistage_output_range")
+        return self.ws[off.value:off.value + nbytes.value].view(len(self.preds) * years, stride.value)
+
+    def from_conv1(self, year_flags, return_probs=True):
+        """__call__ for the batch whose first-conv outputs are already in the workspace (conv1_slot, filled by
+        dta_conv1_multistage_gather_windows, which also set year_flags): the grouped forward without its first convs
+        (dta_conv1_multistage_predict)."""
+        return self._run_conv1(return_probs, None, year_flags)
+
+    def ensemble_from_conv1(self, year_flags, labels=None, return_probs=True):
+        """ensemble() for such a batch (dta_conv1_multistage_predict_ensemble)."""
+        if self.hierarchy is None:
+            raise RuntimeError("MultiStagePredictor.ensemble needs a hierarchy (MultiStagePredictor(models, hierarchy=...))")
+        if self.hierarchy.levels != len(self.preds):
+            raise ValueError("the hierarchy has {} levels, the predictor {}".format(self.hierarchy.levels, len(self.preds)))
+        if labels is not None:
+            labels = _species_labels(labels, self.device)
+            if self.confusion is None:
+                self.confusion = torch.zeros(self.hierarchy.n_species, self.hierarchy.n_species, dtype=torch.int64, device=self.device)
+        self._run_conv1(return_probs, (labels,), year_flags)
+        return self._ens
+
+    def _run_conv1(self, return_probs, ens, year_flags):
+        L = _lib.lib()
+        st = _lib.current_stream_ptr()
+        nl = len(self.preds)
+        Y = len(self.preds[0].nets_mod)
+        if self._key is None or tuple(self._key[0][2:]) != (11, 11) or len(self._key[2]) != Y:
+            raise RuntimeError("no first-conv output in the workspace: fill conv1_slot() first")
+        if (not isinstance(year_flags, torch.Tensor) or year_flags.dtype != torch.float32 or tuple(year_flags.shape) != (Y,)
+                or year_flags.device != self.device):
+            raise ValueError("year_flags must be a float32 [{}] tensor on {}".format(Y, self.device))
+        gate = year_flags.repeat(nl)                # the (level, year) groups' flags: the years' flags once per level
+        # frozen weights: these calls leave every re-layout but the first layer's row table behind, so they may reuse what a
+        # call of either kind packed, while the full forward (_run) reuses only what a full forward packed
+        reuse = self.frozen and (self._packed or self._packed_conv1)
+        desc = self.desc_reuse if reuse else self.desc
+        if ens is None:
+            _lib.check(L.dta_conv1_multistage_predict(C.byref(desc), nl, self.lv, self.nets, _lib.ptr(gate), _lib.ptr(self.ws),
+                                                      self._pp if return_probs else None, self._pi, self._ps, st),
+                       "dta_conv1_multistage_predict")
+        else:
+            labels, = ens
+            B = self._key[0][0]
+            if labels is not None and labels.shape[0] != B:
+                raise ValueError("one species label per crop")
+            if self._ens is None or self._ens[0].shape[0] != B:
+                self._ens = _ensemble_buffers(B, self.device)
+            table = self.hierarchy.c_table(self.device)
+            _lib.check(L.dta_conv1_multistage_predict_ensemble(C.byref(desc), nl, self.lv, self.nets, _lib.ptr(gate), _lib.ptr(self.ws),
+                                                               self._pp if return_probs else None, self._pi, self._ps, C.byref(table),
+                                                               _lib.ptr(self._ens[0]), _lib.ptr(self._ens[1]), _lib.ptr(self._ens[2]),
+                                                               _lib.ptr(labels), _lib.ptr(self.confusion if labels is not None else None), st),
+                       "dta_conv1_multistage_predict_ensemble")
+        self._packed_conv1 = True
+        self._live = (labels if ens is not None else None, gate)
+        return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(nl)]
 
     def _run(self, images, return_probs, present, ens, year_flags=None):
         L = _lib.lib()

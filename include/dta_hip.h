@@ -717,6 +717,59 @@ int dta_conv1_output_range(const dta_net_desc* d, size_t* offset, size_t* bytes)
 int dta_conv1_forward(const dta_net_desc* d, const dta_subnet_params* nets, const double* alpha, void* workspace,
                           float* const scores[2][3], float* joint, void* stream);
 
+/* ---- ... for a multi-stage model (dta_multistage_*: levels x years spectral networks, every level's year-y network on
+ * year y's raster): ONE table per year with the levels side by side, ONE gather launch per batch for all levels x years,
+ * then the grouped forward behind its first convs.  d is the multi-stage descriptor (kind DTA_NET_SPECTRAL, 11x11).
+ *
+ * A year's table: [(height + 2) * (width + 2) + 1][9][levels * 32], columns 32 l .. 32 l + 31 the first conv of level l's
+ * year-y network -- each 32-column slice holds the bits dta_raster_conv1_table gives for that network alone; storage as
+ * above.  Its mask: one byte per table position, 1 where the raster pixel under it has a non-zero stored element (NaN
+ * counts; for a bf16 raster the bf16 values), 0 on the ring and in the far-outside row.  A missing year (raster == NULL)
+ * gets a table of the far-outside row alone ([9][levels * 32]: the biases -- what the first conv gives on an all-zero
+ * input) and a mask of one zero byte.
+ * Sizes per raster pixel: 9 x 32 x levels x 2 B of table in half (4 B in fp32), and 9 x 32 x levels x 4 B of T in the
+ * scratch, which the years share (build them one after the other on one stream).  5 levels at 256x256: 189 MB of table
+ * per year plus 377 MB of scratch.
+ * dta_conv1_multistage_table_bytes: height == width == 0 asks for a missing year's sizes (no scratch). */
+int dta_conv1_multistage_table_bytes(const dta_net_desc* d, int levels, int height, int width, size_t* scratch_bytes,
+                                     size_t* table_bytes, size_t* mask_bytes);
+/* nets: `levels` parameter tables, level l's year-y network at nets[l] (conv_w[0] and conv_b[0] are read).  raster: the
+ * year's normalised raster in the form of d->dtype, or NULL for a missing year (height, width and scratch are then not
+ * used).  raster, scratch and table 16-byte aligned.  Four launches (weight image, tap GEMM, class sums, mask). */
+int dta_conv1_multistage_raster_table(const dta_net_desc* d, int levels, const dta_subnet_params* nets, const void* raster,
+                                      int height, int width, void* scratch, void* table, unsigned char* mask, void* stream);
+/* Where the grouped forward keeps its first convs' outputs inside the workspace of dta_multistage_workspace_bytes: group g
+ * (network lv[l].first + year) at offset + g * group_stride, [batch * 121][32] in the storage format above; bytes =
+ * group_stride * networks. */
+int dta_conv1_multistage_output_range(const dta_net_desc* d, int levels, const dta_level* lv, size_t* offset,
+                                      size_t* group_stride, size_t* bytes);
+/* The first convs of n (<= d->batch) windows for every level x year in ONE launch: level l's 32 columns of
+ * A_y[o_m + (i, j)][rc(i)][cc(j)] go to row m * 121 + i * 11 + j of group lv[l].first + y in `workspace` (a pure copy in
+ * 16-byte pieces; every level must have `years` networks).  tables / masks: HOST arrays of `years` device pointers as
+ * dta_conv1_multistage_raster_table left them; present: HOST array, present[y] == 0 marks a missing year's one-row table
+ * (every position reads it); at least one year must be present.  height / width: the present years' rasters.
+ * flags [years] float32: 1 where any position of the batch's windows has its mask byte set, else 0 -- for an fp32 raster
+ * exactly what dta_year_flags says about the float32 batch dta_gather_windows_years would have written.  Bank protocol
+ * of dta_gather_windows_years (flags zero on entry; clear_next zeroed for the next call, or NULL: flags cleared first).
+ * Plain stores only: no atomics. */
+int dta_conv1_multistage_gather_windows(const dta_net_desc* d, int levels, const dta_level* lv, int years,
+                                        const void* const* tables, const unsigned char* const* masks, const int* present,
+                                        int height, int width, const int* origins, int n, void* workspace, float* flags,
+                                        float* clear_next, void* stream);
+/* dta_multistage_predict / dta_multistage_predict_ensemble for a workspace whose first-conv outputs are ALREADY in place
+ * (dta_conv1_multistage_gather_windows): no inputs, no input pack job, no row table and no conv launch for the first
+ * layer of any group; everything behind it, the epilogue included, is the code of those two calls.  Eval mode
+ * (training == 0) with DTA_FORWARD_ONLY and 11x11 patches only.  DTA_REUSE_PACKED: dta_conv1_forward's contract (these calls
+ * do not leave the first layer's row table behind). */
+int dta_conv1_multistage_predict(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
+                                 const float* gate, void* workspace, float* const* probs, long long* const* top_idx,
+                                 float* const* top_score, void* stream);
+int dta_conv1_multistage_predict_ensemble(const dta_net_desc* d, int levels, const dta_level* lv, const dta_subnet_params* nets,
+                                          const float* gate, void* workspace, float* const* probs, long long* const* top_idx,
+                                          float* const* top_score, const dta_hierarchy* table, long long* ens_label,
+                                          float* ens_score, int* ens_level, const long long* labels, long long* confusion,
+                                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,10 +27,16 @@ launches of one batch) and reported as achieved bytes/s: bytes = 32 read + 32 wr
 A multi-stage model (levels x years bf16 spectral networks, a chain hierarchy) over the windows of `boxes` crown boxes:
   leg A : calls the parent commit has: per-year dta_gather_windows into MultiStagePredictor.ensemble(present=None) (which
           launches dta_year_flags), the same device copies, then per-level dense.crown_reduce + engine.resolve_hierarchy;
-  leg B : dense.predict_windows_multistage (dta_gather_windows_years, ensemble(year_flags=...), dta_crown_resolve).
-Both legs start from resident rasters and share one MultiStagePredictor warmed before the timed region; timed as above.
+  leg B : dense.predict_windows_multistage (dta_gather_windows_years, ensemble(year_flags=...), dta_crown_resolve);
+  leg C : leg B with share_conv1=True on bf16-resident rasters: every year's first convs of all levels once per raster
+          (dense.Conv1TableYears, built inside the timed call), then per batch ONE gather of their outputs and the grouped
+          forward without its first convs.  Its per-window ens_labels are compared with B's, next to B's margin census (the
+          windows where some level's top-2 margin is below 1e-2); `C_below_B_median_by_more_than_B_spread` is the
+          acceptance.  The table build is also timed alone.
+All legs start from resident rasters and share one MultiStagePredictor warmed before the timed region; timed as above.
 Window and crown labels of the legs are compared.  One batch is also timed in pieces (20 back-to-back repeats between
 events): gather + flags each way, and the forward + epilogue chain with and without its own dta_year_flags launch.
+--only B,C alternates the two routes of this package without leg A.
 Prints one JSON line."""
 import argparse
 import json
@@ -60,7 +66,7 @@ def _timed(fn, reps=20):
 def multistage(a):
     import ctypes as C
     from deeptreeattention_amd import _lib
-    from deeptreeattention_amd.dense import DenseRaster, crown_reduce, predict_windows_multistage, window_origins
+    from deeptreeattention_amd.dense import Conv1TableYears, DenseRaster, crown_reduce, predict_windows_multistage, window_origins
     from deeptreeattention_amd.engine import MultiStagePredictor, resolve_hierarchy
     from deeptreeattention_amd.hierarchy import Hierarchy
     from deeptreeattention_amd.year import learned_ensemble
@@ -126,13 +132,23 @@ def multistage(a):
         crown = resolve_hierarchy(h, [c.top_idx for c in per], [c.top_score for c in per])
         return ens[0], crown[0], crown[1]
 
+    margins = {}
+
     def leg_b():
         res = predict_windows_multistage(pred, rs, o, crown_offsets=offsets, batch_size=B)
+        margins["B"] = [t[:, 0] - t[:, 1] for t in res.top_score]
         return res.ens_label, res.crowns.label, res.crowns.score
 
-    legs = {"A": leg_a, "B": leg_b}
-    if a.only:
-        legs = {k: legs[k] for k in a.only.split(",")}
+    rs16 = None
+
+    def leg_c():
+        res = predict_windows_multistage(pred, rs16, o, crown_offsets=offsets, batch_size=B, share_conv1=True)
+        return res.ens_label, res.crowns.label, res.crowns.score
+
+    legs = {"A": leg_a, "B": leg_b, "C": leg_c}
+    legs = {k: legs[k] for k in (a.only.split(",") if a.only else ("A", "B"))}
+    if "C" in legs:      # resident like leg B's, in the form the shared first conv reads
+        rs16 = [None if r is None else DenseRaster(r, precision="bf16", device=dev) for r in raws]
     ms, wall, last = {k: [] for k in legs}, {k: [] for k in legs}, {}
     for rep in range(a.warmup + a.repeats):
         for k, fn in legs.items():
@@ -153,7 +169,7 @@ def multistage(a):
         out["legs"][k] = {"event_ms": [round(v, 2) for v in ms[k]], "median_ms": round(statistics.median(ms[k]), 2),
                           "min_ms": round(min(ms[k]), 2), "max_ms": round(max(ms[k]), 2),
                           "wall_median_ms": round(statistics.median(wall[k]), 2)}
-    if len(last) == 2:
+    if "A" in last and "B" in last:
         A, Bv = last["A"], last["B"]
         out["window_labels_identical"] = bool(torch.equal(A[0], Bv[0]))
         out["crown_labels_identical"] = bool(torch.equal(A[1], Bv[1]))
@@ -163,6 +179,21 @@ def multistage(a):
         out["B_spread_ms"] = round(lb["max_ms"] - lb["min_ms"], 2)
         out["B_below_A_median_by_more_than_both_spreads"] = bool(lb["median_ms"] < la["median_ms"] - max(out["A_spread_ms"], out["B_spread_ms"]))
         out["speedup_A_over_B"] = round(la["median_ms"] / lb["median_ms"], 3)
+    if "B" in last and "C" in last:
+        Bl, Cl = out["legs"]["B"], out["legs"]["C"]
+        out["B_spread_ms"] = round(Bl["max_ms"] - Bl["min_ms"], 2)
+        out["C_below_B_median_by_more_than_B_spread"] = bool(Cl["median_ms"] < Bl["median_ms"] - out["B_spread_ms"])
+        out["speedup_B_over_C"] = round(Bl["median_ms"] / Cl["median_ms"], 3)
+        differ = last["C"][0] != last["B"][0]
+        close = torch.stack([m < 1e-2 for m in margins["B"]]).any(dim=0)
+        out["C_ens_label_differs_from_B"] = int(differ.sum())
+        out["C_ens_label_differs_where_every_B_margin_at_least_1e-2"] = int((differ & ~close).sum())
+        out["B_windows_with_a_level_margin_below_1e-2"] = int(close.sum())
+        out["C_crown_label_differs_from_B"] = int((last["C"][1] != last["B"][1]).sum())
+    if "C" in legs:      # the once-per-call cost: per present year weight image + tap GEMM + class sums + mask
+        Conv1TableYears(rs16, pred)
+        out["conv1_table_years"] = {"us_per_build": round(_timed(lambda: Conv1TableYears(rs16, pred), reps=5), 1),
+                                    "table_MB_per_year": round(((a.side + 2) ** 2 + 1) * 9 * 32 * nl * 2 / 1e6, 1)}
     # one batch in pieces
     ob = o[:B]
     xs = [b[:B] for b in bufs]
@@ -192,6 +223,18 @@ def multistage(a):
     out["per_batch_us"]["forward_chain_with_own_year_flags"] = round(_timed(lambda: pred.ensemble(xs, present=None)), 1)
     out["per_batch_us"]["forward_chain_given_year_flags"] = round(_timed(lambda: pred.ensemble(xs, year_flags=flags)), 1)
     out["per_batch_us"]["year_flags"] = [float(v) for v in flags.cpu().tolist()]
+    if "C" in legs:
+        table = Conv1TableYears(rs16, pred)
+
+        def gather_c():
+            f, nx = banks[state["b"]], banks[state["b"] ^ 1]
+            state["b"] ^= 1
+            state["flags_c"] = table.gather(ob, pred, f, nx)
+
+        out["per_batch_us"]["C_gather_conv1_windows_years"] = round(_timed(gather_c), 1)
+        flags_c = state["flags_c"].clone()
+        out["per_batch_us"]["forward_chain_behind_the_first_convs"] = round(_timed(lambda: pred.ensemble_from_conv1(flags_c)), 1)
+        out["per_batch_us"]["year_flags_C"] = [float(v) for v in flags_c.cpu().tolist()]
     line = json.dumps(out)
     print(line)
     if a.out:
