@@ -7,7 +7,8 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.hierarchy  <->  src/models/multi_stage.py:368-485 (the levels' predictions -> one species label)
     deeptreeattention_amd.dense      <->  src/patches.py:50-83 + src/main.py:165-205: per-pixel windows of a resident raster,
                                      gathered and predicted on the device, reduced per crown; with a multi-stage model
-                                     one species label per pixel and per crown
+                                     one species label per pixel and per crown; and src/patches.py:5-30 +
+                                     src/utils.py:59-79: one resized crop per crown box, cut out of that raster
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.
@@ -19,7 +20,9 @@ from .loop import validate, validate_multistage  # noqa: F401
 from .dense import DenseRaster, window_origins, predict_windows, predict_map  # noqa: F401
 from .dense import predict_windows_multistage, predict_map_multistage, crown_resolve  # noqa: F401
 from .dense import predict_windows_metadata, predict_map_metadata  # noqa: F401
+from .dense import crop_boxes, predict_crops, predict_crops_multistage, predict_crops_metadata  # noqa: F401
 
 __all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
            "validate", "validate_multistage", "DenseRaster", "window_origins", "predict_windows", "predict_map",
-           "predict_windows_multistage", "predict_map_multistage", "crown_resolve"]
+           "predict_windows_multistage", "predict_map_multistage", "crown_resolve",
+           "crop_boxes", "predict_crops", "predict_crops_multistage", "predict_crops_metadata"]

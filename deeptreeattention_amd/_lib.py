@@ -284,6 +284,13 @@ def lib():
         L.dta_gather_windows_years.restype = C.c_int
         L.dta_gather_windows_years.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
                                                C.POINTER(C.c_void_p), vp, vp, vp]
+        L.dta_gather_crops.restype = C.c_int
+        L.dta_gather_crops.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.dta_gather_crops_tiles.restype = C.c_int
+        L.dta_gather_crops_tiles.argtypes = L.dta_gather_crops.argtypes
+        L.dta_gather_crops_years.restype = C.c_int
+        L.dta_gather_crops_years.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_void_p), vp, vp, vp]
         L.dta_crown_resolve.restype = C.c_int
         L.dta_crown_resolve.argtypes = [C.c_int, C.POINTER(C.c_void_p), vp, C.c_int, C.POINTER(HierarchyTable), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, vp, vp, vp, vp, vp]

@@ -163,6 +163,18 @@ __device__ __forceinline__ float to_f(float v) { return v; }
 __device__ __forceinline__ float to_f(short v) { return (float)v; }
 __device__ __forceinline__ float to_f(unsigned char v) { return (float)v; }
 
+// ATen's nearest-neighbour source index (what torchvision's NEAREST resize dispatches to):
+// min(floor(dst * float(in / out)), in - 1).  ONE definition for k_preprocess_crops* (preprocess.hip) and the crop gathers
+// (dense.hip): the resized crop of a box equals the index selection from the normalised raster only while both use it.
+// An integer dst * in / out is NOT this function.  The scale is split off so that a lane can keep it per box.
+__device__ __forceinline__ float nearest_scale(int in, int out) { return (float)in / (float)out; }
+__device__ __forceinline__ int nearest_at(int dst, float scale, int in) {
+#pragma clang fp contract(off)
+  const int i = (int)floorf((float)dst * scale);
+  return i < in - 1 ? i : in - 1;
+}
+__device__ __forceinline__ int nearest_src(int dst, int in, int out) { return nearest_at(dst, nearest_scale(in, out), in); }
+
 }  // namespace dta
 
 // hipFuncSetAttribute is a per-device setting: a launch site remembers per device ordinal whether it has made it (one

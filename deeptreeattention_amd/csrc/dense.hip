@@ -8,6 +8,8 @@
 // and for a multi-stage model (levels x years networks on the same windows, engine.MultiStagePredictor):
 //   k_gather_windows_years  one batch of windows out of every year's raster in ONE launch, with the years' 0/1 flags
 //   k_crown_resolve         every level's per-crown mean and top-2, the hierarchy walk on them and the crown's window votes
+// and for the reference's production path (one crop per crown box, resized to SxS with NEAREST; src/patches.py:5-30):
+//   k_gather_crops[_tiles|_years]  N boxes -> the resized crops, an index selection from the resident raster
 // All are bandwidth-bound copies or short reductions: no float atomics, fixed summation order, bit-identical reruns.
 #include "../../include/dta_hip.h"
 #include "kernels.h"
@@ -148,6 +150,114 @@ __global__ __launch_bounds__(256) void k_gather_windows_tiles(GatherArgs a) {
   if (rr >= 0 && rr < a.H && cc >= 0 && cc < a.W) {
     const size_t plane = (size_t)a.H * a.W;
     v = reinterpret_cast<const u32x4*>(a.raster)[((size_t)ch * plane + (size_t)rr * a.W + (size_t)cc) * 2 + half];
+  }
+  reinterpret_cast<u32x4*>(a.out)[id] = v;
+}
+
+// ---- crops: a crown's box cut out of the raster and resized to S x S with NEAREST (reference src/patches.py:5-30 `crop`,
+// src/utils.py:59-79 `load_image`).  The normalisation is per pixel position and a NEAREST resize only selects pixels, so
+// the resized, preprocessed crop of a box is an index selection from the normalised raster: output pixel (i, j) reads
+// raster pixel (row0 + nearest_src(i, h, S), col0 + nearest_src(j, w, S)) -- nearest_src (common.h) is the very function
+// k_preprocess_crops resizes with, which is what makes the two bit-identical.  flip: output (i, j) takes the resized
+// pixel (S - 1 - i, S - 1 - j), both training flips (src/augmentation.py:13-14), as k_preprocess_crops applies them.
+// A box with no rows or no columns: an all-zero crop (the dataset's fill for a missing crop, data.py:295-296).  Every
+// read is guarded: a source position outside the raster reads 0, whatever the box says; offsets into the raster 64-bit.
+struct CropBox { long long row0, col0; int h, w; float sh, sw; };
+__device__ __forceinline__ CropBox crop_box(const int* boxes, int n, int S) {
+  const int* b = boxes + (size_t)n * 4;
+  const int r0 = b[0], c0 = b[1], r1 = b[2], c1 = b[3];
+  CropBox x;
+  x.row0 = r0; x.col0 = c0;
+  x.h = (int)((unsigned)r1 - (unsigned)r0); x.w = (int)((unsigned)c1 - (unsigned)c0);      // (a side past 2^31 wraps: guarded reads)
+  x.sh = nearest_scale(x.h, S); x.sw = nearest_scale(x.w, S);
+  return x;
+}
+// the raster offset output pixel (i, j) of box b reads, or -1: nothing to read (an empty box, a position off the raster)
+__device__ __forceinline__ long long crop_src(const CropBox& b, int i, int j, int S, int flip, int H, int W) {
+  if (b.h <= 0 || b.w <= 0) return -1;
+  if (flip) { i = S - 1 - i; j = S - 1 - j; }
+  const long long rr = b.row0 + nearest_at(i, b.sh, b.h), cc = b.col0 + nearest_at(j, b.sw, b.w);
+  if (rr < 0 || rr >= H || cc < 0 || cc >= W) return -1;
+  return rr * W + cc;
+}
+
+// float32 NCHW batch [N][C][S][S]: gather_lane's scheme -- a lane owns four consecutive floats of the flat batch and does
+// one 16-byte store; its four may straddle rows, planes and crops, and a lane that steps into the next crop reloads that
+// crop's box.  (ONE definition for k_gather_crops and k_gather_crops_years.)  Returns whether any of the lane's elements
+// is non-zero (NaN counts as non-zero).
+__device__ __forceinline__ bool crop_lane(const CropGatherArgs& a, size_t q4) {
+  const size_t total = (size_t)a.N * a.C * a.S * a.S;
+  const size_t e = q4 * 4;
+  if (e >= total) return false;
+  const int S = a.S, SS = S * S;
+  const size_t per = (size_t)a.C * SS;
+  int n = (int)(e / per);
+  int r = (int)(e - (size_t)n * per);
+  int c = r / SS, q = r - c * SS;
+  int i = q / S, j = q - i * S;
+  const float* ras = reinterpret_cast<const float*>(a.raster);
+  const size_t plane = (size_t)a.H * a.W;
+  CropBox b = crop_box(a.boxes, n, S);
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    v[k] = 0.f;
+    if (e + k < total) {
+      const long long src = crop_src(b, i, j, S, a.flip, a.H, a.W);
+      if (src >= 0) v[k] = ras[(size_t)c * plane + (size_t)src];
+      if (++j == S) {
+        j = 0;
+        if (++i == S) {
+          i = 0;
+          if (++c == a.C) {
+            c = 0; ++n;
+            if (n < a.N) b = crop_box(a.boxes, n, S);
+          }
+        }
+      }
+    }
+  }
+  float* out = reinterpret_cast<float*>(a.out);
+  if (e + 4 <= total) *reinterpret_cast<f32x4*>(out + e) = f32x4{v[0], v[1], v[2], v[3]};
+  else for (int k = 0; e + k < total; ++k) out[e + k] = v[k];
+  return !(v[0] == 0.f && v[1] == 0.f && v[2] == 0.f && v[3] == 0.f);
+}
+__global__ __launch_bounds__(256) void k_gather_crops(CropGatherArgs a) {
+  crop_lane(a, (size_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// The same boxes out of every year's raster: blockIdx.y = year, every year the lanes and bytes of k_gather_crops; a missing
+// year (NULL) writes nothing.  flags / clear_next: k_gather_windows_years' protocol, word for word.
+__global__ __launch_bounds__(256) void k_gather_crops_years(CropGatherYearsArgs a) {
+  const int y = blockIdx.y;
+  if (a.clear_next && blockIdx.x == 0 && threadIdx.x == 0) a.clear_next[y] = 0.f;
+  if (!a.rasters[y]) return;
+  CropGatherArgs g = a.g;
+  g.raster = a.rasters[y]; g.out = a.outs[y];
+  const bool hit = crop_lane(g, (size_t)blockIdx.x * 256 + threadIdx.x);
+  const bool any = __any(hit);
+  if (any && (threadIdx.x & 63) == 0) a.flags[y] = 1.f;
+}
+
+// The first conv's bf16 tiles [N][NC][S*S][16] out of the bf16 raster [NC][P][16], as k_gather_windows_tiles: a lane moves
+// one 16-byte half of a (crop, chunk, pixel) element, consecutive lanes consecutive halves -- the stores of a wave are one
+// contiguous run, its loads the selected pixels of the box's rows (an upsampled box: the same 32 bytes several times).
+__global__ __launch_bounds__(256) void k_gather_crops_tiles(CropGatherArgs a) {
+  const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int S = a.S, SS = S * S, NC = (a.C + 15) / 16;
+  const size_t total = (size_t)a.N * NC * SS * 2;
+  if (id >= total) return;
+  const int half = (int)(id & 1);
+  const size_t el = id >> 1;
+  const int q = (int)(el % SS);
+  const size_t t = el / SS;
+  const int ch = (int)(t % NC), n = (int)(t / NC);
+  const int i = q / S, j = q - i * S;
+  const long long src = crop_src(crop_box(a.boxes, n, S), i, j, S, a.flip, a.H, a.W);
+  u32x4 v = u32x4{0u, 0u, 0u, 0u};
+  if (src >= 0) {
+    const size_t plane = (size_t)a.H * a.W;
+    v = reinterpret_cast<const u32x4*>(a.raster)[((size_t)ch * plane + (size_t)src) * 2 + half];
   }
   reinterpret_cast<u32x4*>(a.out)[id] = v;
 }
@@ -337,6 +447,36 @@ int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st) {
   if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_windows_tiles: batch too large for one launch"); return 1; }
   hipLaunchKernelGGL(k_gather_windows_tiles, dim3((unsigned)blocks), dim3(256), 0, st, a);
   DTA_CHECK_LAUNCH("k_gather_windows_tiles");
+  return 0;
+}
+
+int launch_gather_crops(const CropGatherArgs& a, hipStream_t st) {
+  const size_t total = (size_t)a.N * a.C * a.S * a.S, lanes = (total + 3) / 4;
+  const size_t blocks = (lanes + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_crops: batch too large for one launch"); return 1; }
+  hipLaunchKernelGGL(k_gather_crops, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_gather_crops");
+  return 0;
+}
+
+int launch_gather_crops_years(const CropGatherYearsArgs& a, hipStream_t st) {
+  const size_t total = (size_t)a.g.N * a.g.C * a.g.S * a.g.S, lanes = (total + 3) / 4;
+  const size_t blocks = (lanes + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_crops_years: batch too large for one launch"); return 1; }
+  if (a.years < 1 || a.years > MAXG) { dta_set_error("dta_gather_crops_years: 1..%d years", MAXG); return 1; }
+  // flags must be zero on entry: cleared here, unless the caller alternates two banks and lets each call clear the other
+  if (!a.clear_next && hipMemsetAsync(a.flags, 0, sizeof(float) * a.years, st) != hipSuccess) { dta_set_error("dta_gather_crops_years: memset failed"); return 1; }
+  hipLaunchKernelGGL(k_gather_crops_years, dim3((unsigned)blocks, a.years), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_gather_crops_years");
+  return 0;
+}
+
+int launch_gather_crops_tiles(const CropGatherArgs& a, hipStream_t st) {
+  const size_t total = (size_t)a.N * ((a.C + 15) / 16) * a.S * a.S * 2;
+  const size_t blocks = (total + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_crops_tiles: batch too large for one launch"); return 1; }
+  hipLaunchKernelGGL(k_gather_crops_tiles, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH("k_gather_crops_tiles");
   return 0;
 }
 

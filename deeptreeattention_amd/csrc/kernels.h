@@ -696,6 +696,15 @@ int launch_crown_reduce(const CrownArgs& a, hipStream_t st);
 // written) into that year's batch, with the years' 0/1 flags (k_year_flags' meaning and bank protocol)
 struct GatherYearsArgs { const float* rasters[MAXG]; float* outs[MAXG]; GatherArgs g; int years; float* flags; float* clear_next; };
 int launch_gather_windows_years(const GatherYearsArgs& a, hipStream_t st);
+// crops: boxes [N][4] int32 (row0, col0, row1, col1), half-open, in raster pixels, anywhere; each box resized to S x S with
+// NEAREST (nearest_src, common.h), flip != 0: both flips after the resize.  A source position outside the raster reads 0;
+// a box with no rows or no columns gives an all-zero crop.  Layouts as the window gathers'.
+struct CropGatherArgs { const void* raster; const int* boxes; void* out; int N, C, H, W, S, flip; };
+int launch_gather_crops(const CropGatherArgs& a, hipStream_t st);          // float32 [C][H][W] -> float32 [N][C][S][S]
+int launch_gather_crops_tiles(const CropGatherArgs& a, hipStream_t st);    // bf16 chunks -> bf16 [N][ceil(C / 16)][S * S][16]
+// the same boxes out of every year's float32 raster: GatherYearsArgs' meaning of rasters / outs / flags / clear_next
+struct CropGatherYearsArgs { const float* rasters[MAXG]; float* outs[MAXG]; CropGatherArgs g; int years; float* flags; float* clear_next; };
+int launch_gather_crops_years(const CropGatherYearsArgs& a, hipStream_t st);
 // every level's per-crown mean (may be NULL) / top-2 as k_crown_reduce, the crowns' count, the walk on the levels' top-1
 // (e: table and ens_* outputs per crown; e.labels / e.confusion unused) and -- win_label / votes both or neither -- the
 // number of a crown's windows whose own label is each species: votes int32 [n_crowns][e.n_species]

@@ -24,12 +24,7 @@ struct CropArgs {
   int B, Craw, c0, C, S, flip, pitch, cc, np;   // np: output pixels per workgroup (a crop is split into SS/np workgroups)
 };
 
-// ATen's nearest-neighbour source index: min(floor(dst * float(in / out)), in - 1)
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-  const float scale = (float)in / (float)out;
-  const int i = (int)floorf((float)dst * scale);
-  return i < in - 1 ? i : in - 1;
-}
+// (the NEAREST resize's source index: nearest_src, common.h -- shared with the crop gathers of dense.hip)
 
 // LAYOUT 0: raw[c][h][w]   LAYOUT 1: raw[h][w][c]
 template <typename T, int LAYOUT>

@@ -30,6 +30,20 @@ For the site-metadata fusion model (engine.MetadataPredictor; every window of a 
                                  per batch (dta_meta_predict with the raster's site); with crown offsets also crown_reduce
     predict_map_metadata         a label map and a score map of a raster region
 
+For the reference's production path -- ONE crop per crown: patches.crop (src/patches.py:5-30) cuts the crown's bounding box out
+of the tile, utils.load_image (src/utils.py:59-79) preprocesses it and resizes it to 11x11 with NEAREST -- the same per-pixel
+argument goes one step further: a NEAREST resize only selects pixels, so the resized, preprocessed crop of a box is an index
+selection from the normalised raster, bit for bit what preprocess.preprocess_batch gives for the host-sliced raw crop:
+
+    crop_boxes                   pixel boxes -> boxes clipped to the raster as rasterio's non-boundless read clips (host)
+    DenseRaster.crops            boxes -> the float32 batch or the first conv's bf16 tiles, resized to size x size, with the
+                                 training flips on request (dta_gather_crops[_tiles]); crops_years: every year in ONE launch
+                                 with the years' flags (dta_gather_crops_years)
+    predict_crops, predict_crops_multistage, predict_crops_metadata
+                                 the three loops above with that gather in place of the window gather: one row per box; with
+                                 one crop per crown the multi-stage result is the reference's gather_predictions + ensemble
+    (no share_conv1 here: a resized crop's 3x3 neighbours are not raster neighbours unless the box is exactly 11x11)
+
 The species of a crown with several windows is THIS package's definition: per level the mean over the crown's windows
 (crown_reduce_np), then the walk over the levels' top-1 of those means (Hierarchy.resolve_np).  The reference has none: its
 `gather_predictions` (multi_stage.py:368-402) takes a flat argmax over one row per individual.  With one window per crown
@@ -53,7 +67,7 @@ precision): every level's year-y network reads year y's raster, so a year's firs
                                  (dta_conv1_multistage_gather_windows); the grouped forward then starts behind its first
                                  convs (dta_conv1_multistage_predict_ensemble)
 
-`gather_windows_np`, `crown_reduce_np` and `crown_resolve_np` are the written-down meaning of the gather, reduce and
+`gather_windows_np`, `gather_crops_np`, `crown_reduce_np` and `crown_resolve_np` are the written-down meaning of the gathers, reduce and
 resolve kernels, `conv1_table_np` and `gather_conv1_np` that of the first-conv table and its gather, `conv1_mask_np`,
 `gather_conv1_years_np` and `year_flags_np` that of the multi-stage form.
 File reading and georeferencing stay with the caller, as in preprocess.py."""
@@ -102,6 +116,56 @@ def gather_windows_np(raster_norm, origins, size=WINDOW):
         ra, rb, ca, cb = max(r, 0), min(r + size, Hh), max(c, 0), min(c + size, Ww)
         if ra < rb and ca < cb:
             out[n, :, ra - r:rb - r, ca - c:cb - c] = raster_norm[:, ra:rb, ca:cb]
+    return out
+
+
+def crop_boxes(boxes, height, width, empty="raise"):
+    """boxes: pixel boxes (row0, col0, row1, col1), half-open.  Each is clipped to the raster [0, height) x [0, width): what
+    rasterio's non-boundless read(window=...) of the reference's patches.crop returns is the intersection.  An empty
+    intersection raises ValueError naming the box (reference patches.py:13-14); with empty="zero" it becomes the
+    degenerate box (0, 0, 0, 0), which DenseRaster.crops turns into an all-zero crop.  Returns int32 [N, 4].  A pure host
+    function."""
+    if empty not in ("raise", "zero"):
+        raise ValueError("empty must be 'raise' or 'zero', got {!r}".format(empty))
+    b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    out = np.stack([np.clip(b[:, 0], 0, height), np.clip(b[:, 1], 0, width),
+                    np.clip(b[:, 2], 0, height), np.clip(b[:, 3], 0, width)], axis=1)
+    none = (out[:, 2] <= out[:, 0]) | (out[:, 3] <= out[:, 1])
+    if none.any():
+        if empty == "raise":
+            k = int(np.flatnonzero(none)[0])
+            raise ValueError("box {} {} does not intersect the {} x {} raster".format(k, tuple(int(v) for v in b[k]), height, width))
+        out[none] = 0
+    return out.astype(np.int32)
+
+
+def nearest_index(out_size, in_size):
+    """The source index of a NEAREST resize from in_size to out_size (ATen, what torchvision dispatches to):
+    min(floor(dst * float32(in / out)), in - 1), in float32 -- an integer dst * in // out is not the same function."""
+    scale = np.float32(in_size) / np.float32(out_size)
+    idx = np.floor(np.arange(out_size, dtype=np.float32) * scale).astype(np.int64)
+    return np.minimum(idx, in_size - 1)
+
+
+def gather_crops_np(raster_norm, boxes, size=WINDOW, flip=False):
+    """What dta_gather_crops computes: raster_norm [C][H][W] -> [N][C][size][size]; crop n is box n = (row0, col0, row1,
+    col1) of the raster resized to size x size with NEAREST: pixel (i, j) is raster pixel (row0 + nearest_index(size, h)[i],
+    col0 + nearest_index(size, w)[j]), a position outside the raster zero.  flip: both axes reversed after the resize (the
+    training flips).  A box with h <= 0 or w <= 0: zeros.  A pure selection: the raster's dtype and bits."""
+    raster_norm = np.asarray(raster_norm)
+    boxes = np.asarray(boxes).reshape(-1, 4)
+    Cb, Hh, Ww = raster_norm.shape
+    out = np.zeros((len(boxes), Cb, size, size), dtype=raster_norm.dtype)
+    for n, (r0, c0, r1, c1) in enumerate(boxes):
+        h, w = int(r1) - int(r0), int(c1) - int(c0)
+        if h <= 0 or w <= 0:
+            continue
+        rows, cols = int(r0) + nearest_index(size, h), int(c0) + nearest_index(size, w)
+        if flip:
+            rows, cols = rows[::-1], cols[::-1]
+        inside = ((rows >= 0) & (rows < Hh))[:, None] & ((cols >= 0) & (cols < Ww))[None, :]
+        picked = raster_norm[:, np.clip(rows, 0, Hh - 1)][:, :, np.clip(cols, 0, Ww - 1)]
+        out[n] = np.where(inside[None], picked, np.zeros((), dtype=raster_norm.dtype))
     return out
 
 
@@ -313,23 +377,27 @@ class DenseRaster:
         t = self.data.view(-1, self.height * self.width, 16).view(torch.bfloat16).float()      # [chunk][pixel][16]
         return t.permute(0, 2, 1).reshape(-1, self.height, self.width)[:self.bands].contiguous()
 
-    def _origins(self, origins):
-        if isinstance(origins, torch.Tensor):
-            o = origins
+    def _index(self, items, cols, what):
+        """origins [N, 2] / boxes [N, 4]: a host array or a device tensor -> a contiguous int32 device tensor."""
+        if isinstance(items, torch.Tensor):
+            o = items
             if o.dtype != torch.int32 or o.device != self.device or not o.is_contiguous():
                 o = o.to(device=self.device, dtype=torch.int32).contiguous()
         else:
-            o = torch.from_numpy(np.ascontiguousarray(np.asarray(origins, dtype=np.int32))).to(self.device)
-        if o.dim() != 2 or o.shape[1] != 2 or o.shape[0] < 1:
-            raise ValueError("origins must be a non-empty [N, 2] array of (row, col)")
+            o = torch.from_numpy(np.ascontiguousarray(np.asarray(items, dtype=np.int32))).to(self.device)
+        if o.dim() != 2 or o.shape[1] != cols or o.shape[0] < 1:
+            raise ValueError(what)
         return o
 
-    def windows(self, origins, tiles=False, size=WINDOW, out=None):
-        """origins: [N, 2] int32 (row, col) of each window's top-left corner (host array or device tensor); may hang over
-        the raster's edges (zero fill).  Returns the float32 (N, bands, size, size) batch (an fp32 raster), or with
-        tiles=True a preprocess.PatchTiles (a bf16 raster).  out: the buffer to write (same shape / element count)."""
+    def _origins(self, origins):
+        return self._index(origins, 2, "origins must be a non-empty [N, 2] array of (row, col)")
+
+    def _boxes(self, boxes):
+        return self._index(boxes, 4, "boxes must be a non-empty [N, 4] array of (row0, col0, row1, col1)")
+
+    def _gather(self, entry, o, extra, tiles, size, out):
+        """The body of windows / crops: `entry`[_tiles](raster, bands, H, W, o, N, size, *extra, out, stream)."""
         L = _lib.lib()
-        o = self._origins(origins)
         N = o.shape[0]
         if tiles:
             if self.precision != "bf16":
@@ -339,8 +407,8 @@ class DenseRaster:
                 out = torch.empty(numel, dtype=torch.int16, device=self.device)
             elif out.dtype != torch.int16 or out.numel() != numel or not out.is_contiguous():
                 raise ValueError("out must be a contiguous int16 tensor of {} elements".format(numel))
-            _lib.check(L.dta_gather_windows_tiles(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N,
-                                                  size, _lib.ptr(out), _lib.current_stream_ptr()), "dta_gather_windows_tiles")
+            _lib.check(getattr(L, entry + "_tiles")(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N,
+                                                    size, *extra, _lib.ptr(out), _lib.current_stream_ptr()), entry + "_tiles")
             return PatchTiles(out, N, self.bands, size, size)
         if self.precision != "fp32":
             raise RuntimeError("the float32 batch needs DenseRaster(..., precision='fp32')")
@@ -349,10 +417,24 @@ class DenseRaster:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32 tensor of shape {}".format(shape))
-        _lib.check(L.dta_gather_windows(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N, size,
-                                        _lib.ptr(out), _lib.current_stream_ptr()), "dta_gather_windows")
+        _lib.check(getattr(L, entry)(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N, size, *extra,
+                                     _lib.ptr(out), _lib.current_stream_ptr()), entry)
         return out
 
+    def windows(self, origins, tiles=False, size=WINDOW, out=None):
+        """origins: [N, 2] int32 (row, col) of each window's top-left corner (host array or device tensor); may hang over
+        the raster's edges (zero fill).  Returns the float32 (N, bands, size, size) batch (an fp32 raster), or with
+        tiles=True a preprocess.PatchTiles (a bf16 raster).  out: the buffer to write (same shape / element count)."""
+        return self._gather("dta_gather_windows", self._origins(origins), (), tiles, size, out)
+
+    def crops(self, boxes, tiles=False, size=WINDOW, train=False, out=None):
+        """boxes: [N, 4] int32 (row0, col0, row1, col1), half-open (host array or device tensor).  Each box is cut out of
+        the raster and resized to size x size with NEAREST -- the reference's patches.crop + utils.load_image, bit for bit
+        what preprocess.preprocess_batch gives for the host-sliced raw crop (gather_crops_np; dta_gather_crops[_tiles]).
+        train=True: both training flips after the resize.  A box with no rows or columns gives an all-zero crop (a missing
+        crop); the boxes are taken as they are -- pixels of a box outside the raster read 0, clip with crop_boxes for the
+        reference's intersection.  Returns what windows() returns, in the same forms; out: the buffer to write."""
+        return self._gather("dta_gather_crops", self._boxes(boxes), (int(bool(train)),), tiles, size, out)
 
     def conv1_table(self, predictor, size=WINDOW):
         """The first conv of `predictor`'s network over this raster, once (dta_raster_conv1_table): a Conv1Table in the
@@ -363,18 +445,15 @@ class DenseRaster:
         return Conv1Table(self, pred)
 
     @staticmethod
-    def windows_years(rasters, origins, outs, flags, clear_next, size=WINDOW):
-        """DenseRaster.windows for every year of an ensemble in ONE launch (dta_gather_windows_years).  rasters: one fp32
-        DenseRaster per year (same shape), None for a missing year; outs: one contiguous float32 (N, bands, size, size)
-        tensor per year -- a missing year's is not written (keep it zero); flags / clear_next: two float32 [years] device
-        tensors used alternately by successive calls (dta_year_flags' banks: `flags` zero on entry, `clear_next` zeroed by
-        this call).  flags ends as dta_year_flags' verdict on the years' batches.  Returns flags."""
+    def _gather_years(entry, rasters, items, cols, outs, flags, clear_next, size, extra):
+        """The body of windows_years / crops_years: `entry`(rasters, Y, bands, H, W, o, N, size, *extra, outs, flags,
+        clear_next, stream)."""
         rs = list(rasters)
         have = _check_years(rs)
         r0 = have[0]
         if len(outs) != len(rs):
             raise ValueError("one output batch per year")
-        o = r0._origins(origins)
+        o = r0._origins(items) if cols == 2 else r0._boxes(items)
         N, Y = o.shape[0], len(rs)
         shape = (N, r0.bands, size, size)
         for t in outs:
@@ -386,9 +465,25 @@ class DenseRaster:
         L = _lib.lib()
         rp = (_lib.C.c_void_p * Y)(*[None if r is None else r.data.data_ptr() for r in rs])
         op = (_lib.C.c_void_p * Y)(*[t.data_ptr() for t in outs])
-        _lib.check(L.dta_gather_windows_years(rp, Y, r0.bands, r0.height, r0.width, _lib.ptr(o), N, size, op, _lib.ptr(flags),
-                                              _lib.ptr(clear_next), _lib.current_stream_ptr()), "dta_gather_windows_years")
+        _lib.check(getattr(L, entry)(rp, Y, r0.bands, r0.height, r0.width, _lib.ptr(o), N, size, *extra, op, _lib.ptr(flags),
+                                     _lib.ptr(clear_next), _lib.current_stream_ptr()), entry)
         return flags
+
+    @staticmethod
+    def windows_years(rasters, origins, outs, flags, clear_next, size=WINDOW):
+        """DenseRaster.windows for every year of an ensemble in ONE launch (dta_gather_windows_years).  rasters: one fp32
+        DenseRaster per year (same shape), None for a missing year; outs: one contiguous float32 (N, bands, size, size)
+        tensor per year -- a missing year's is not written (keep it zero); flags / clear_next: two float32 [years] device
+        tensors used alternately by successive calls (dta_year_flags' banks: `flags` zero on entry, `clear_next` zeroed by
+        this call).  flags ends as dta_year_flags' verdict on the years' batches.  Returns flags."""
+        return DenseRaster._gather_years("dta_gather_windows_years", rasters, origins, 2, outs, flags, clear_next, size, ())
+
+    @staticmethod
+    def crops_years(rasters, boxes, outs, flags, clear_next, size=WINDOW, train=False):
+        """DenseRaster.crops for every year of an ensemble in ONE launch (dta_gather_crops_years): all years the same
+        boxes.  rasters / outs / flags / clear_next as windows_years takes them; train=True: both flips.  Returns flags."""
+        return DenseRaster._gather_years("dta_gather_crops_years", rasters, boxes, 4, outs, flags, clear_next, size,
+                                         (int(bool(train)),))
 
 
 def _share_conv1_refusals(pred, raster, size):
@@ -655,6 +750,24 @@ def raster_precision(model_or_predictor):
     return "bf16" if tiles else "fp32"
 
 
+# What the prediction loops gather per batch: windows at origins [N, 2] or resized crops of boxes [N, 4].  The loops
+# (_predict_batches*) are written once and take one of these two.
+#   index(raster, items)  the caller's origins / boxes -> the int32 device tensor the gathers take, once, before the loop
+#   one(raster, idx, ...) a batch out of one raster (DenseRaster.windows / .crops)
+#   years                 a batch out of every year's raster in one launch (DenseRaster.windows_years / .crops_years)
+_Gather = collections.namedtuple("_Gather", "index one years")
+
+
+def _clipped_boxes(raster, boxes):
+    """Raw pixel boxes (host array or tensor) -> crop_boxes of them on the device."""
+    host = boxes.detach().cpu().numpy() if isinstance(boxes, torch.Tensor) else boxes
+    return raster._boxes(crop_boxes(host, raster.height, raster.width))
+
+
+_WINDOWS = _Gather(DenseRaster._origins, DenseRaster.windows, DenseRaster.windows_years)
+_CROPS = _Gather(_clipped_boxes, DenseRaster.crops, DenseRaster.crops_years)
+
+
 def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, batch_size=4096, return_probs=False,
                     share_conv1=False):
     """Per-window prediction on 11x11 windows (the side every prediction route here is tested at; DenseRaster.windows
@@ -671,7 +784,25 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
     forward without its first conv -- no window of the input is ever formed.  Anything it does not cover raises
     RuntimeError before a launch (_share_conv1_refusals).
     Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None)."""
-    L = _lib.lib()
+    return _predict_batches(_WINDOWS, model_or_predictor, rasters, origins, crown_offsets, batch_size, return_probs, share_conv1)
+
+
+def predict_crops(model_or_predictor, rasters, boxes, batch_size=4096, return_probs=False):
+    """One prediction per crown box, as the reference's production path defines it (predict.py -> generate_crops ->
+    patches.crop -> utils.load_image): each box is cut out of the resident raster and resized to 11x11 with NEAREST on the
+    device (DenseRaster.crops), then predict_windows' loop -- the eval forward, dta_softmax_top2 -- in batches of
+    `batch_size`; nothing inside the loop waits for the device, and no crop passes through the host: one raster upload,
+    16 bytes per crown.  boxes: pixel boxes (row0, col0, row1, col1), half-open; they go through crop_boxes once, before
+    the loop (clipped to the raster; a box that misses it raises ValueError).  rasters: as for predict_windows, including
+    one per year (None: a missing year) for a year.learned_ensemble.
+    There is no share_conv1 here: a resized crop's 3x3 neighbours are not raster neighbours unless the box is exactly
+    11x11, so the first conv's output at a crop position is not a function of the raster pixel underneath.
+    Returns WindowPredictions(top_idx [N, 2], top_score [N, 2], probs or None, crowns=None): one row per box."""
+    return _predict_batches(_CROPS, model_or_predictor, rasters, boxes, None, batch_size, return_probs, False)
+
+
+def _predict_batches(gather, model_or_predictor, rasters, items, crown_offsets, batch_size, return_probs, share_conv1):
+    """The loop of predict_windows / predict_crops."""
     pred = _predictor(model_or_predictor)
     size = WINDOW
     if share_conv1:
@@ -697,7 +828,8 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
         if r.shape != r0.shape:
             raise ValueError("all years' rasters must share one shape")
     dev = r0.device
-    o = r0._origins(origins)
+    o = gather.index(r0, items)
+    L = _lib.lib()
     N, classes = o.shape[0], pred.nets_mod[0]._classes
     keep = return_probs or crown_offsets is not None
     top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
@@ -725,9 +857,9 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
             logits = pred.logits_from_conv1()
         else:
             if tiles:
-                x = r0.windows(ob, tiles=True, size=size, out=bufs[0][:n * per])
+                x = gather.one(r0, ob, tiles=True, size=size, out=bufs[0][:n * per])
             else:
-                xs = [b[:n] if r is None else r.windows(ob, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
+                xs = [b[:n] if r is None else gather.one(r, ob, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
                 x = xs if pred.ensemble else xs[0]
             logits = pred.logits_of(x)
         _lib.check(L.dta_softmax_top2(_lib.ptr(logits), n, classes, _lib.ptr(probs[n0:n0 + n]) if keep else None,
@@ -802,11 +934,26 @@ def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, 
     allocated (_share_conv1_multistage_refusals).
     Returns MultiStageWindowPredictions(ens_label int64 [N], ens_score float32 [N], ens_level int32 [N], top_idx / top_score:
     one [N, 2] tensor per level, probs: one [N, classes_l] tensor per level or None, crowns: CrownSpecies or None)."""
+    return _predict_batches_multistage(_WINDOWS, predictor, rasters, origins, crown_offsets, batch_size, return_probs, share_conv1)
+
+
+def predict_crops_multistage(predictor, rasters, boxes, batch_size=4096, return_probs=False):
+    """One species per crown box from a multi-stage model: predict_crops' crops (ONE gather launch for all years per batch,
+    dta_gather_crops_years, which also decides the years' flags) through predict_windows_multistage's loop.  With one crop
+    per crown this is exactly the reference's gather_predictions + ensemble (multi_stage.py:368-485) on the crops its
+    predict.predict_species generates.  predictor / rasters as for predict_windows_multistage (fp32 rasters, None: a
+    missing year); boxes as for predict_crops (crop_boxes once, before the loop).  No share_conv1: see predict_crops.
+    Returns MultiStageWindowPredictions, one row per box, crowns=None."""
+    return _predict_batches_multistage(_CROPS, predictor, rasters, boxes, None, batch_size, return_probs, False)
+
+
+def _predict_batches_multistage(gather, predictor, rasters, items, crown_offsets, batch_size, return_probs, share_conv1):
+    """The loop of predict_windows_multistage / predict_crops_multistage."""
     rs = _multistage_years(predictor, rasters)
     have = _share_conv1_multistage_refusals(predictor, rs, WINDOW) if share_conv1 else _check_years(rs)
     r0 = have[0]
     dev, size, Y = r0.device, WINDOW, len(rs)
-    o = r0._origins(origins)
+    o = gather.index(r0, items)
     N = o.shape[0]
     if crown_offsets is not None:
         crown_offsets = _host_offsets(crown_offsets, N)
@@ -838,7 +985,7 @@ def predict_windows_multistage(predictor, rasters, origins, crown_offsets=None, 
             e = predictor.ensemble_from_conv1(flags, return_probs=keep)
         else:
             xs = [b[:n] for b in bufs]
-            flags = DenseRaster.windows_years(rs, o[n0:n0 + n], xs, banks[bank], banks[bank ^ 1], size=size)
+            flags = gather.years(rs, o[n0:n0 + n], xs, banks[bank], banks[bank ^ 1], size=size)
             bank ^= 1
             e = predictor.ensemble(xs, year_flags=flags, return_probs=keep)
         for dst, src in zip(ens, e):
@@ -887,6 +1034,19 @@ def predict_windows_metadata(predictor, raster, site, origins, crown_offsets=Non
     device.  predictor: an engine.MetadataPredictor (its table is built once, before the loop).  raster: a DenseRaster in
     the form raster_precision(predictor.sensor) names.  site: the raster's site index, one int.
     Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None) as predict_windows does."""
+    return _predict_batches_metadata(_WINDOWS, predictor, raster, site, origins, crown_offsets, batch_size, return_probs)
+
+
+def predict_crops_metadata(predictor, raster, site, boxes, batch_size=4096, return_probs=False):
+    """predict_crops for the site-metadata fusion model: the crops of predict_crops through predict_windows_metadata's
+    loop (the sensor model's eval forward, then dta_meta_predict with the raster's site for every row).  predictor /
+    raster / site as for predict_windows_metadata; boxes as for predict_crops.  No share_conv1: see predict_crops.
+    Returns WindowPredictions, one row per box, crowns=None."""
+    return _predict_batches_metadata(_CROPS, predictor, raster, site, boxes, None, batch_size, return_probs)
+
+
+def _predict_batches_metadata(gather, predictor, raster, site, items, crown_offsets, batch_size, return_probs):
+    """The loop of predict_windows_metadata / predict_crops_metadata."""
     from .engine import MetadataPredictor
     if not isinstance(predictor, MetadataPredictor):
         raise TypeError("the metadata route needs an engine.MetadataPredictor")
@@ -900,7 +1060,7 @@ def predict_windows_metadata(predictor, raster, site, origins, crown_offsets=Non
     if not 0 <= site < predictor.sites:
         raise ValueError("site {} is outside [0, {})".format(site, predictor.sites))
     dev, size = raster.device, WINDOW
-    o = raster._origins(origins)
+    o = gather.index(raster, items)
     N, classes = o.shape[0], predictor.classes
     if crown_offsets is not None:
         crown_offsets = _host_offsets(crown_offsets, N)
@@ -921,7 +1081,7 @@ def predict_windows_metadata(predictor, raster, site, origins, crown_offsets=Non
     for n0 in range(0, N, B):
         n = min(B, N - n0)
         ob = o[n0:n0 + n]
-        x = raster.windows(ob, tiles=True, size=size, out=buf[:n * per]) if tiles else raster.windows(ob, size=size, out=buf[:n])
+        x = gather.one(raster, ob, tiles=True, size=size, out=buf[:n * per]) if tiles else gather.one(raster, ob, size=size, out=buf[:n])
         scores = sens.logits_of(x)
         predictor.head(scores, n, ws, site, None, probs[n0:n0 + n] if keep else None, top_idx[n0:n0 + n], top_score[n0:n0 + n])
     crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None

@@ -659,6 +659,35 @@ int dta_crown_reduce(const float* probs, const long long* offsets, int n_crowns,
  * the next call, with clear_next == NULL the call clears flags itself first.  Plain stores only: no atomics. */
 int dta_gather_windows_years(const float* const* rasters, int years, int bands, int height, int width, const int* origins,
                              int n, int size, float* const* outs, float* flags, float* clear_next, void* stream);
+/* ---- Crops of crown boxes out of the resident raster: the reference's production prediction path (src/patches.py:5-30
+ * `crop` cuts a crown's bounding box out of the tile, src/utils.py:59-79 `load_image` preprocesses it and resizes it to
+ * size x size with NEAREST).  The preprocessing is per pixel position and a NEAREST resize only selects pixels, so the
+ * resized, preprocessed crop of a box is an index selection from the normalised raster, bit for bit what
+ * dta_preprocess_crops[_tiles] writes for the host-sliced raw crop.
+ *
+ * boxes [n][4] int32 = (row0, col0, row1, col1), half-open, in raster pixels, device memory; h = row1 - row0,
+ * w = col1 - col0.  Output pixel (i, j) of crop k reads raster pixel
+ *   (row0 + min(floor(i * float32(h / size)), h - 1), col0 + min(floor(j * float32(w / size)), w - 1))
+ * -- the float32 arithmetic of ATen's nearest index, the one dta_preprocess_crops resizes with (an integer i * h / size is
+ * not the same function).  flip != 0: output pixel (i, j) takes the resized pixel (size - 1 - i, size - 1 - j), both
+ * training flips after the resize (dta_crop_desc.flip).  A box with h <= 0 or w <= 0 gives an all-zero crop (the
+ * reference dataset's fill for a missing crop, data.py:295-296).  A source position outside the raster reads 0: a box
+ * that was not clipped to the raster never reads out of bounds (clip boxes on the host to get the reference's
+ * intersection; dense.crop_boxes).  size 1..4096; n >= 1.
+ *
+ * dta_gather_crops:        float32 raster [bands][height][width] -> out float32 [n][bands][size][size]
+ * dta_gather_crops_tiles:  bf16 chunks [ceil(bands / 16)][height * width][16] -> tiles bf16 [n][ceil(bands / 16)][size * size][16]
+ * dta_gather_crops_years:  dta_gather_crops for every year of an ensemble in ONE launch, all years the same boxes; rasters /
+ *                          outs / flags / clear_next exactly as dta_gather_windows_years takes them (a NULL raster: a
+ *                          missing year, nothing written, flag 0; flags from the values on their way out, NaN counts as
+ *                          non-zero; the bank protocol of dta_year_flags).
+ * raster and out / tiles 16-byte aligned.  Pure copies: no atomics, reruns are bit-identical. */
+int dta_gather_crops(const float* raster, int bands, int height, int width, const int* boxes, int n, int size, int flip,
+                     float* out, void* stream);
+int dta_gather_crops_tiles(const void* raster, int bands, int height, int width, const int* boxes, int n, int size, int flip,
+                           void* tiles, void* stream);
+int dta_gather_crops_years(const float* const* rasters, int years, int bands, int height, int width, const int* boxes,
+                           int n, int size, int flip, float* const* outs, float* flags, float* clear_next, void* stream);
 /* One species per crown out of per-window, per-level probabilities, in ONE launch: for every level what dta_crown_reduce
  * gives on probs[l] [rows][table->classes[l]] (mean[l] [n_crowns][classes_l] -- `mean` or single entries may be NULL --,
  * top_idx[l] / top_score[l] [n_crowns][2], bit for bit; count [n_crowns] once), then what dta_hierarchy_resolve gives on

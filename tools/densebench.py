@@ -37,6 +37,17 @@ All legs start from resident rasters and share one MultiStagePredictor warmed be
 Window and crown labels of the legs are compared.  One batch is also timed in pieces (20 back-to-back repeats between
 events): gather + flags each way, and the forward + epilogue chain with and without its own dta_year_flags launch.
 --only B,C alternates the two routes of this package without leg A.
+
+    python tools/densebench.py --crops [--side 256] [--boxes 4096] [--min-side 3] [--max-side 25] [--batch 4096] ...
+
+One crop per crown box, resized to 11x11 with NEAREST (the reference's production path), bf16 Hang2020:
+  leg A : what the parent commit offers: every box sliced from the raw host raster, preprocess.preprocess_batch(tiles=True)
+          (one upload and one launch per batch), engine.Predictor, dta_softmax_top2;
+  leg B : dense.DenseRaster (one upload, one normalise launch, inside the timed call) + dense.predict_crops;
+  leg B_resident : dense.predict_crops on a raster that is already resident (reported, not part of the acceptance).
+One Predictor for all legs, warmed before the timed region; legs alternate, timed as above; their top-2 labels are compared.
+`B_below_A_median_and_ranges_apart` is the acceptance.  The crop gather launch is also timed alone (20 back-to-back launches
+of one batch) and reported as bytes written per second next to the measured copy figure.
 Prints one JSON line."""
 import argparse
 import json
@@ -243,8 +254,100 @@ def multistage(a):
             f.write(line + "\n")
 
 
+def crops(a):
+    from deeptreeattention_amd import Hang2020 as H
+    from deeptreeattention_amd import _lib
+    from deeptreeattention_amd.dense import DenseRaster, predict_crops
+    from deeptreeattention_amd.engine import Predictor
+    from deeptreeattention_amd.preprocess import preprocess_batch
+    dev = torch.device("cuda:0")
+    S = 11
+    rng = np.random.default_rng(7)
+    raw = rng.integers(-500, 9000, size=(a.bands, a.side, a.side), dtype=np.int16)
+    hs, ws = (rng.integers(a.min_side, a.max_side + 1, size=a.boxes) for _ in range(2))
+    r0, c0 = rng.integers(0, a.side - hs + 1), rng.integers(0, a.side - ws + 1)
+    boxes = np.stack([r0, c0, r0 + hs, c0 + ws], axis=1).astype(np.int32)
+    N = len(boxes)
+    torch.manual_seed(3)
+    model = H.Hang2020(a.bands - 20, a.classes, precision="bf16").to(dev).eval()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pred = Predictor(model)
+    pred(torch.zeros(min(a.batch, N), a.bands - 20, S, S, device=dev), return_probs=False)
+    torch.cuda.synchronize()
+    setup_ms = (time.perf_counter() - t0) * 1e3
+
+    def leg_a():
+        top = torch.empty(N, 2, dtype=torch.int64, device=dev)
+        for n0 in range(0, N, a.batch):
+            bb = boxes[n0:n0 + a.batch]
+            x = preprocess_batch([raw[:, p:q, u:v] for p, u, q, v in bb], S, device=dev, tiles=True)
+            top[n0:n0 + len(bb)] = pred(x, return_probs=False)[1]
+        return top
+
+    resident = DenseRaster(raw, precision="bf16", device=dev)
+    legs = {"A": leg_a,
+            "B": lambda: predict_crops(pred, DenseRaster(raw, precision="bf16", device=dev), boxes, batch_size=a.batch).top_idx,
+            "B_resident": lambda: predict_crops(pred, resident, boxes, batch_size=a.batch).top_idx}
+    if a.only:
+        legs = {k: legs[k] for k in a.only.split(",")}
+    ms, wall, last = {k: [] for k in legs}, {k: [] for k in legs}, {}
+    for rep in range(a.warmup + a.repeats):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            last[k] = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                ms[k].append(e0.elapsed_time(e1))
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+    raw_bytes = int((hs * ws).sum()) * a.bands * raw.itemsize
+    out = {"tool": "densebench --crops", "build": _lib.lib().dta_build_id().decode(), "side": a.side, "bands_raw": a.bands,
+           "classes": a.classes, "boxes": N, "box_sides": [a.min_side, a.max_side], "batch": a.batch, "repeats": a.repeats,
+           "warmup": a.warmup, "predictor_setup_ms": round(setup_ms, 2),
+           "host_link_bytes": {"A_raw_crops": raw_bytes, "B_raster_plus_boxes": raw.nbytes + boxes.nbytes,
+                               "B_resident_boxes": boxes.nbytes}, "legs": {}}
+    for k in legs:
+        out["legs"][k] = {"event_ms": [round(v, 2) for v in ms[k]], "median_ms": round(statistics.median(ms[k]), 2),
+                          "min_ms": round(min(ms[k]), 2), "max_ms": round(max(ms[k]), 2),
+                          "wall_median_ms": round(statistics.median(wall[k]), 2), "wall_min_ms": round(min(wall[k]), 2),
+                          "wall_max_ms": round(max(wall[k]), 2)}
+    if "A" in last and "B" in last:
+        A, B = out["legs"]["A"], out["legs"]["B"]
+        out["top2_labels_identical"] = bool(torch.equal(last["A"], last["B"]))
+        # host work is most of leg A: the acceptance is on the host clock around the synchronised call
+        out["B_below_A_median_and_ranges_apart"] = bool(B["wall_median_ms"] < A["wall_median_ms"] and B["wall_max_ms"] < A["wall_min_ms"])
+        out["B_below_A_event_median_and_ranges_apart"] = bool(B["median_ms"] < A["median_ms"] and B["max_ms"] < A["min_ms"])
+        out["speedup_A_over_B_wall"] =round(A["wall_median_ms"] / B["wall_median_ms"], 2)
+    # the crop gather alone: one batch, 20 back-to-back launches between two events
+    n = min(a.batch, N)
+    bb = torch.from_numpy(boxes[:n]).to(dev)
+    buf = resident.crops(bb, tiles=True).tiles
+    us = _timed(lambda: resident.crops(bb, tiles=True, out=buf))
+    written = n * ((resident.bands + 15) // 16) * S * S * 32
+    out["gather_crops_tiles"] = {"crops": n, "bytes_written": written, "us_per_launch": round(us, 1),
+                                 "written_TB_per_s": round(written / us / 1e6, 3), "copy_probe_TB_per_s": 5.8}
+    r32 = DenseRaster(raw, precision="fp32", device=dev)
+    buf32 = r32.crops(bb)
+    us32 = _timed(lambda: r32.crops(bb, out=buf32))
+    out["gather_crops_fp32"] = {"crops": n, "bytes_written": buf32.numel() * 4, "us_per_launch": round(us32, 1),
+                                "written_TB_per_s": round(buf32.numel() * 4 / us32 / 1e6, 3), "copy_probe_TB_per_s": 5.8}
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--crops", action="store_true")
+    ap.add_argument("--min-side", type=int, default=3)
+    ap.add_argument("--max-side", type=int, default=25)
     ap.add_argument("--side", type=int, default=256)
     ap.add_argument("--bands", type=int, default=369)
     ap.add_argument("--classes", type=int, default=200)
@@ -264,6 +367,10 @@ def main():
         raise SystemExit("densebench needs the GPU (no fallback)")
     if a.multistage:
         return multistage(a)
+    if a.crops:
+        if a.boxes == 64:      # (--boxes' default belongs to --multistage)
+            a.boxes = 4096
+        return crops(a)
     from deeptreeattention_amd import Hang2020 as H
     from deeptreeattention_amd import _lib
     from deeptreeattention_amd.dense import DenseRaster, predict_windows, window_origins
