@@ -91,6 +91,7 @@ class HierarchyTable(C.Structure):  # dta_hierarchy
 
 
 ADAM_MAX_SEGMENTS = 16   # DTA_ADAM_MAX_SEGMENTS
+ABUNDANCE_MAX_SPECIES = 256   # DTA_ABUNDANCE_MAX_SPECIES
 
 
 class MetaParams(C.Structure):      # dta_meta_params
@@ -327,6 +328,14 @@ def lib():
         L.dta_conv1_multistage_predict_ensemble.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(Level), C.POINTER(SubnetParams),
                                                             vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                             C.POINTER(C.c_void_p), C.POINTER(HierarchyTable), vp, vp, vp, vp, vp, vp]
+        # species abundance: counts and confusion resampling (abundance.hip)
+        L.dta_abundance_workspace_bytes.restype = C.c_size_t
+        L.dta_abundance_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int]
+        L.dta_abundance_resample.restype = C.c_int
+        L.dta_abundance_resample.argtypes = [vp, vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, vp,
+                                             vp, C.c_size_t, vp]
+        L.dta_abundance_counts.restype = C.c_int
+        L.dta_abundance_counts.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_size_t, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

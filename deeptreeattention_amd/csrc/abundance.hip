@@ -1,0 +1,167 @@
+// Species abundance with uncertainty (reference src/multinomial.py + sample_multinomial.py: 100 passes of pandas lambdas
+// over every predicted crown; abundance.py: the plain count).  deeptreeattention_amd/abundance.py holds the definition
+// (resample_np / counts_np); these kernels equal it bit for bit: a draw is decided by 64-bit integer arithmetic and ONE
+// float32 comparison, the counts are integer sums.
+//   k_abundance_resample  every iteration of the resampling in ONE launch: a workgroup owns a slice of crowns and a group of
+//                         AB_G iterations, counts into an LDS histogram [AB_G][species + 1] and stores it whole (zeros
+//                         included) as its slice's partial histogram
+//   k_abundance_sum       counts[t][b] = the sum of the slices' partial histograms: a store pass and a per-destination sum
+//                         pass instead of global atomics, so nothing has to be cleared and nothing is left behind
+// No float atomics, no global atomics at all; the table (species^2 thresholds, 160 KB at 200 species) is left to L2.
+#include "../../include/dta_hip.h"
+#include "common.h"
+
+namespace dta {
+
+constexpr int AB_G = 8;              // iterations per workgroup: a crown's label, score and mask byte are read once for them
+constexpr int AB_THREADS = 256;
+constexpr int AB_CROWNS = 1024;      // a slice is at least this long (while there are crowns) ...
+constexpr int AB_WORKGROUPS = 2048;  // ... and longer once slices x iteration groups would pass this many workgroups
+constexpr unsigned long long AB_GOLDEN = 0x9E3779B97F4A7C15ull;
+
+struct AbundanceArgs {
+  const long long* label; const float* score; const unsigned char* mask; long long n;
+  const unsigned* table; int S, iterations;
+  unsigned long long key_keep, key_draw, first;   // the two stream keys (host: ab_key) and first_iteration
+  long long per;                                  // crowns per slice
+  unsigned long long* part;                       // [slices][iterations][S + 1]
+};
+
+// splitmix64's finaliser (abundance.py: _mix)
+__host__ __device__ __forceinline__ unsigned long long ab_mix(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+static unsigned long long ab_key(unsigned long long seed, unsigned stream) { return ab_mix(seed * AB_GOLDEN + stream + 1ull); }
+
+__global__ __launch_bounds__(AB_THREADS) void k_abundance_resample(AbundanceArgs a) {
+  __shared__ unsigned hist[AB_G * (DTA_ABUNDANCE_MAX_SPECIES + 1)];
+  const int S = a.S, bins = S + 1, tid = threadIdx.x;
+  const int t0 = blockIdx.x * AB_G;
+  const int nt = a.iterations - t0 < AB_G ? a.iterations - t0 : AB_G;
+  for (int e = tid; e < nt * bins; e += AB_THREADS) hist[e] = 0u;
+  __syncthreads();
+  const long long i0 = (long long)blockIdx.y * a.per;
+  const long long i1 = i0 + a.per < a.n ? i0 + a.per : a.n;
+  const unsigned long long N = (unsigned long long)a.n;
+  const unsigned long long step = N * AB_GOLDEN;             // the counter grows by N per iteration
+  for (long long i = i0 + tid; i < i1; i += AB_THREADS) {
+    if (a.mask && a.mask[i] == 0) continue;                  // clipped away by the caller: counted nowhere
+    const long long lab = a.label[i];
+    if (lab < 0 || lab >= S || !a.score) {                   // DEAD / unresolved: bin S; no scores: every crown keeps
+      const int bin = (lab < 0 || lab >= S) ? S : (int)lab;
+      for (int t = 0; t < nt; ++t) atomicAdd(&hist[t * bins + bin], 1u);
+      continue;
+    }
+    const int l = (int)lab;
+    const float sc = a.score[i];
+    const unsigned* row = a.table + (size_t)l * S;
+    // ((first + t0 + t) * N + i) * GOLDEN, formed in 64 bits and modulo 2^64 as the mirror forms it
+    unsigned long long c = ((a.first + (unsigned long long)t0) * N + (unsigned long long)i) * AB_GOLDEN;
+    for (int t = 0; t < nt; ++t, c += step) {
+      const unsigned r_keep = (unsigned)(ab_mix(c + a.key_keep) >> 40);
+      int bin = l;
+      if ((float)r_keep * 0x1p-24f >= sc) {                  // exact in float32; false for a NaN score: it keeps
+        const unsigned r_draw = (unsigned)(ab_mix(c + a.key_draw) >> 40);
+        // the number of entries <= r_draw of a non-decreasing row: branch-free binary search, S is the same in every lane
+        int base = 0, len = S;
+        while (len > 1) {
+          const int half = len >> 1;
+          base = row[base + half - 1] <= r_draw ? base + half : base;
+          len -= half;
+        }
+        bin = base + (row[base] <= r_draw ? 1 : 0);          // < S: every row ends at 2^24, above every draw
+        bin = bin < S ? bin : S - 1;                         // (a table that breaks that rule cannot leave the histogram)
+      }
+      atomicAdd(&hist[t * bins + bin], 1u);
+    }
+  }
+  __syncthreads();
+  unsigned long long* dst = a.part + ((size_t)blockIdx.y * a.iterations + t0) * bins;
+  for (int e = tid; e < nt * bins; e += AB_THREADS) dst[e] = hist[e];
+}
+
+__global__ __launch_bounds__(AB_THREADS) void k_abundance_sum(const unsigned long long* part, int slices, long long total,
+                                                              long long* counts) {
+  const long long e = (long long)blockIdx.x * AB_THREADS + threadIdx.x;
+  if (e >= total) return;
+  unsigned long long s = 0;
+  for (int k = 0; k < slices; ++k) s += part[(size_t)k * total + e];
+  counts[e] = (long long)s;
+}
+
+struct AbundancePlan { int groups, slices; long long per; size_t bytes; };
+
+// 0 on success; the plan depends on (n, species, iterations) alone, so dta_abundance_workspace_bytes and the calls agree
+static int ab_plan(const char* who, long long n, int species, int iterations, AbundancePlan* p) {
+  if (n < 1) { dta_set_error("%s: bad shape: n=%lld", who, n); return 1; }
+  if (species < 1 || species > DTA_ABUNDANCE_MAX_SPECIES) {
+    dta_set_error("%s: species=%d: 1..%d (DTA_ABUNDANCE_MAX_SPECIES)", who, species, DTA_ABUNDANCE_MAX_SPECIES);
+    return 1;
+  }
+  if (iterations < 0) { dta_set_error("%s: iterations=%d is negative", who, iterations); return 1; }
+  p->groups = (iterations + AB_G - 1) / AB_G;
+  const long long cap = p->groups >= AB_WORKGROUPS ? 1 : AB_WORKGROUPS / (p->groups > 0 ? p->groups : 1);
+  long long slices = (n + AB_CROWNS - 1) / AB_CROWNS;
+  slices = slices > cap ? cap : slices;
+  p->slices = (int)slices;
+  p->per = (n + slices - 1) / slices;
+  if (p->per > 0xFFFFFFFFll) { dta_set_error("%s: n=%lld: too many crowns per workgroup for 32-bit bins", who, n); return 1; }
+  if ((long long)iterations * (species + 1) > 0x7FFFFFFFll * AB_THREADS) { dta_set_error("%s: iterations=%d: too many for one launch", who, iterations); return 1; }
+  p->bytes = sizeof(unsigned long long) * (size_t)slices * (size_t)(iterations > 0 ? iterations : 1) * (size_t)(species + 1);
+  return 0;
+}
+
+static int ab_run(const char* who, const AbundancePlan& p, AbundanceArgs a, long long* counts, void* workspace,
+                  size_t workspace_bytes, hipStream_t st) {
+  if (workspace_bytes < p.bytes) { dta_set_error("%s: workspace too small: %zu bytes, %zu needed", who, workspace_bytes, p.bytes); return 1; }
+  if ((uintptr_t)workspace & 7) { dta_set_error("%s: the workspace must be 8-byte aligned", who); return 1; }
+  a.per = p.per; a.part = (unsigned long long*)workspace;
+  hipLaunchKernelGGL(k_abundance_resample, dim3(p.groups, p.slices), dim3(AB_THREADS), 0, st, a);
+  DTA_CHECK_LAUNCH("k_abundance_resample");
+  const long long total = (long long)a.iterations * (a.S + 1);
+  hipLaunchKernelGGL(k_abundance_sum, dim3((unsigned)((total + AB_THREADS - 1) / AB_THREADS)), dim3(AB_THREADS), 0, st,
+                     (const unsigned long long*)workspace, p.slices, total, counts);
+  DTA_CHECK_LAUNCH("k_abundance_sum");
+  return 0;
+}
+
+}  // namespace dta
+
+using namespace dta;
+
+extern "C" {
+
+size_t dta_abundance_workspace_bytes(long long n, int species, int iterations) {
+  AbundancePlan p;
+  if (ab_plan("dta_abundance_workspace_bytes", n, species, iterations, &p)) return 0;
+  return p.bytes;
+}
+
+int dta_abundance_resample(const long long* label, const float* score, const unsigned char* mask, long long n,
+                           const unsigned int* table, int species, int iterations, unsigned long long seed,
+                           unsigned long long first_iteration, long long* counts, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (!label || !table || !counts || !workspace) { dta_set_error("dta_abundance_resample: null argument"); return 1; }
+  AbundancePlan p;
+  if (ab_plan("dta_abundance_resample", n, species, iterations, &p)) return 1;
+  if (iterations == 0) return 0;                // an empty [0][species + 1]: nothing to write
+  AbundanceArgs a;
+  a.label = label; a.score = score; a.mask = mask; a.n = n; a.table = table; a.S = species; a.iterations = iterations;
+  a.key_keep = ab_key(seed, 0); a.key_draw = ab_key(seed, 1); a.first = first_iteration;
+  return ab_run("dta_abundance_resample", p, a, counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int dta_abundance_counts(const long long* label, const unsigned char* mask, long long n, int species, long long* counts,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  if (!label || !counts || !workspace) { dta_set_error("dta_abundance_counts: null argument"); return 1; }
+  AbundancePlan p;
+  if (ab_plan("dta_abundance_counts", n, species, 1, &p)) return 1;
+  AbundanceArgs a;
+  a.label = label; a.score = nullptr; a.mask = mask; a.n = n; a.table = nullptr; a.S = species; a.iterations = 1;
+  a.key_keep = 0; a.key_draw = 0; a.first = 0;
+  return ab_run("dta_abundance_counts", p, a, counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -799,6 +799,36 @@ int dta_conv1_multistage_predict_ensemble(const dta_net_desc* d, int levels, con
                                           float* ens_score, int* ens_level, const long long* labels, long long* confusion,
                                           void* stream);
 
+/* ---- Species abundance with uncertainty: trees per species over predicted crowns, and the reference's confusion
+ * resampling of that count (src/multinomial.py:28-35, 61-77, run 100 times by sample_multinomial.py; abundance.py's
+ * value_counts is dta_abundance_counts).  Per iteration t and crown i of n:
+ *   counter = (first_iteration + t) * n + i                                       (64 bits, modulo 2^64)
+ *   mix(z)  : z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^ (z >> 31)
+ *   r_keep / r_draw = mix(counter * 0x9E3779B97F4A7C15 + mix(seed * 0x9E3779B97F4A7C15 + stream + 1)) >> 40, stream 0 / 1
+ *   keep    = !(float(r_keep) * 2^-24 >= score[i])        (a NaN score keeps; score == NULL: every crown keeps)
+ *   drawn   = the number of entries of table[label[i]] that are <= r_draw
+ *   counts[t][keep ? label[i] : drawn] += 1
+ * A label outside [0, species) counts in bin `species` whatever its score (DEAD, the walk's unresolved -1); a crown with
+ * mask[i] == 0 (mask may be NULL: none) is counted nowhere.  table: uint32 [species][species], row p for a crown predicted
+ * as p: non-decreasing thresholds in units of 2^-24 whose last entry is 2^24 (deeptreeattention_amd/abundance.py:
+ * sampling_table builds it on the host from a confusion matrix; the rows are NOT checked here).
+ * counts: int64 [iterations][species + 1], OVERWRITTEN in full by the call (not added to; nothing has to be cleared).
+ * Integer sums only, no atomics on global memory: reruns are bit-identical, and equal the host definition
+ * (abundance.resample_np) bit for bit.  Two launches: every iteration in one, then the sum of the workgroups' partial
+ * histograms, which live in `workspace` (dta_abundance_workspace_bytes(n, species, iterations) bytes, 8-byte aligned;
+ * 0 and dta_last_error() for a bad shape).  n >= 1, 1 <= species <= DTA_ABUNDANCE_MAX_SPECIES, iterations >= 0
+ * (0: nothing is launched).  stream: a hipStream_t, as everywhere here. */
+#define DTA_ABUNDANCE_MAX_SPECIES 256
+size_t dta_abundance_workspace_bytes(long long n, int species, int iterations);
+int dta_abundance_resample(const long long* label, const float* score, const unsigned char* mask, long long n,
+                           const unsigned int* table, int species, int iterations, unsigned long long seed,
+                           unsigned long long first_iteration, long long* counts, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* The plain count: counts int64 [species + 1], the same bins and mask, overwritten in full; the workspace of
+ * dta_abundance_workspace_bytes(n, species, 1). */
+int dta_abundance_counts(const long long* label, const unsigned char* mask, long long n, int species, long long* counts,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
