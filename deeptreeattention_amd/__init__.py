@@ -11,6 +11,8 @@ The package mirrors the reference's module names for this path only:
                                      src/utils.py:59-79: one resized crop per crown box, cut out of that raster
     deeptreeattention_amd.abundance  <->  abundance.py + src/multinomial.py: trees per species over the predicted crowns, and
                                      the confusion resampling of that count (every iteration in one launch)
+    deeptreeattention_amd.canopy     <->  src/CHM.py + src/predict.py find_crowns: the 99th-percentile canopy height of every
+                                     crown box of a resident CHM raster and the height rules on it (one launch pair)
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

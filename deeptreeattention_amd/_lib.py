@@ -92,6 +92,12 @@ class HierarchyTable(C.Structure):  # dta_hierarchy
 
 ADAM_MAX_SEGMENTS = 16   # DTA_ADAM_MAX_SEGMENTS
 ABUNDANCE_MAX_SPECIES = 256   # DTA_ABUNDANCE_MAX_SPECIES
+CROWN_WAVE_CELLS = 1024   # DTA_CROWN_WAVE_CELLS
+
+
+class HeightRule(C.Structure):      # dta_height_rule
+    _fields_ = [("mode", C.c_int), ("min_height", C.c_double), ("min_chm", C.c_double), ("max_diff", C.c_double),
+                ("limit", C.c_double)]
 
 
 class MetaParams(C.Structure):      # dta_meta_params
@@ -336,6 +342,10 @@ def lib():
                                              vp, C.c_size_t, vp]
         L.dta_abundance_counts.restype = C.c_int
         L.dta_abundance_counts.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_size_t, vp]
+        # crown height filter: CHM quantile per box and the keep rules (canopy.hip)
+        L.dta_crown_height.restype = C.c_int
+        L.dta_crown_height.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, C.c_float, C.c_float, vp, C.POINTER(HeightRule),
+                                       vp, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -829,6 +829,37 @@ int dta_abundance_resample(const long long* label, const float* score, const uns
 int dta_abundance_counts(const long long* label, const unsigned char* mask, long long n, int species, long long* counts,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Crown height filter: the canopy-height statistic of every crown box of a resident CHM raster, and the reference's keep
+ * rules on it (src/CHM.py:9-14 non_zero_99_quantile, run per crown through rasterstats.zonal_stats; :58-95 height_rules;
+ * src/predict.py:35-42 find_crowns: CHM_height > 3).  chm: float32 [height][width] on the device.  boxes: int32 [n][4] =
+ * (row0, col0, row1, col1), half-open, any int32 values: each box is clipped to the raster.  Per crown i:
+ *   kept   = the cells v of the clipped box with v >= floor, one float32 comparison (drops NaN, nodata, everything under it)
+ *   count  = the number of kept values; 0: out_height = NaN
+ *   virt   = float32(count - 1) * (float32(q) / float32(100));  lo = floor(virt);  t = virt - lo;  hi = min(lo + 1, count - 1)
+ *   a, b   = the lo-th and hi-th smallest kept value (0-based), selected exactly;  d = b - a
+ *   out_height = t >= 0.5 ? b - d * (1 - t) : a + d * t        every operation rounded to float32 on its own (no FMA):
+ * np.nanpercentile's result on float32 input, bit for bit (deeptreeattention_amd/canopy.py: crown_height_np is the definition).
+ * A clipped box of more than 2^24 cells is refused on the device, where the boxes live: out_count = -1, out_height = NaN,
+ * out_keep = 0.  The rule, in double after exact widening (chm = out_height):
+ *   mode 1  keep = chm > min_height                                   (a NaN height is dropped)
+ *   mode 2  with h = field_height[i], in this order: chm NaN: 0; h NaN: 1; chm < min_chm: 0;
+ *           chm > h: !(chm - h >= max_diff); otherwise: !(h - chm >= limit)
+ * out_keep: 0 / 1 bytes [n], NULL exactly when rule is NULL or its mode is 0; field_height: double [n] on the device, read
+ * in mode 2 only.  Every output element is overwritten.  Two launches (one wave per crown of up to DTA_CROWN_WAVE_CELLS
+ * clipped cells; one workgroup per larger crown), no workspace, no atomics on global memory: the result of a crown depends
+ * on its own box alone.  Refused on the host, before any launch: a null chm / boxes / out_height / out_count, n < 1,
+ * height or width < 1, height * width over int32, q outside [0, 100] or NaN, floor not > 0 (kept values must order by their
+ * bit patterns), an unknown mode, mode 2 without field_height, a keep buffer without a rule and the reverse. */
+#define DTA_CROWN_WAVE_CELLS 1024
+typedef struct {
+  int mode;          /* 0 none, 1 min height, 2 height rules */
+  double min_height; /* mode 1 */
+  double min_chm, max_diff, limit;   /* mode 2 */
+} dta_height_rule;
+int dta_crown_height(const float* chm, int height, int width, const int* boxes, long long n, float q, float floor,
+                     const double* field_height, const dta_height_rule* rule, float* out_height, int* out_count,
+                     unsigned char* out_keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
