@@ -1109,8 +1109,10 @@ class EnsembleTrainer(_SingleModelMetrics):
         batch lacks a year that another rank kept contributes nothing to that year's gradient sum."""
         L = _lib.lib()
         if phases & 1:
-            for i in kept:
-                self.years[i]._zero_grads()      # C-ABI contract: gradient buffers arrive zero-filled
+            for t in self.years:
+                # C-ABI contract: gradient buffers arrive zero-filled; a year left out of `kept` has no gradient in this
+                # step (reference year.py:27-28) -- with keep_grads its buffer must not go on showing an earlier step's
+                t._zero_grads()
         _lib.check(L.dta_ensemble_backward_gated(C.byref(self._desc), len(kept), self._nets, _lib.ptr(self._ws),
                                                  _lib.ptr(self.dscores), self._grads, _lib.ptr(gate), phases,
                                                  _lib.current_stream_ptr()), "dta_ensemble_backward")
@@ -1307,12 +1309,16 @@ class MultiStageTrainer:
     #      training_step once per optimizer -- i.e. per level -- on every batch; the levels are independent networks) ----
     def _batchable(self, xs_levels):
         """The levels' steps can share one set of launches when nothing is exchanged between ranks, every level brings the
-        same batch size / crop shape / precision / mode, and the networks fit one grouped launch."""
+        same batch size / crop shape / precision / mode and the same Adam settings (betas, eps, keep_grads; the learning
+        rates may differ), and the networks fit one grouped launch.  Decided before any launch or counter change."""
         if len(self.levels) > _lib.MAX_LEVELS or any(t.comm for t in self.levels):
             return False
         shapes = {tuple(x.shape) for xs in xs_levels for x in xs}
         if len(shapes) != 1:
             return False
+        t0 = self.levels[0]
+        if any(t.betas != t0.betas or t.eps != t0.eps or t.keep_grads != t0.keep_grads for t in self.levels):
+            return False      # one optimizer launch has one set of Adam settings (betas, eps, zero_grad)
         m0 = self.levels[0].model.year_models[0]
         for t in self.levels:
             for m in t.model.year_models:
@@ -1328,7 +1334,8 @@ class MultiStageTrainer:
         segments, each level with its own class weights and learning rate (dta_multistage_*); results are those of
         training_step(batch, ., l) for l = 0, 1, ... in turn.  present: None (missing years decided on the device, no host
         synchronisation), or one list of booleans per level.  Steps the levels one after the other when they cannot share a
-        launch chain (different batch sizes or shapes, more than 16 kept networks, data-parallel trainers)."""
+        launch chain (different batch sizes or shapes, more than 16 kept networks, data-parallel trainers, levels whose
+        betas / eps / keep_grads differ)."""
         nl = len(self.levels)
         if len(batch) != nl:
             raise ValueError("expected one batch per level ({}), got {}".format(nl, len(batch)))
@@ -1392,9 +1399,11 @@ class MultiStageTrainer:
                                         _lib.ptr(self._gate_banks[self._gate_bank ^ 1]), st), "dta_year_flags")
         _lib.check(L.dta_multistage_forward_loss(C.byref(desc), nl, lv_a, nets_a, x_a, _lib.ptr(gate), _lib.ptr(self._ws), st),
                    "dta_multistage_forward_loss")
-        for t, ks in zip(self.levels, kept):
-            for i in ks:
-                t.years[i]._zero_grads()      # C-ABI contract: gradient buffers arrive zero-filled
+        for t in self.levels:
+            for yr in t.years:
+                # C-ABI contract: gradient buffers arrive zero-filled.  A year the caller's `present` leaves out has no
+                # gradient in this step either (reference year.py:27-28): with keep_grads it must not show the last one
+                yr._zero_grads()
         _lib.check(L.dta_multistage_backward(C.byref(desc), nl, lv_a, nets_a, _lib.ptr(self._ws), grads_a, _lib.ptr(gate), st),
                    "dta_multistage_backward")
         # ---- one Adam per level (multi_stage.py:258-262: its own learning rate), all of them in launches of 16 segments ----
@@ -1422,13 +1431,14 @@ class MultiStageTrainer:
             if present is None:
                 t._bank = nxt
                 t.local_flags = gate[lv[l].first:lv[l].first + lv[l].count]
+        # the call's rate is 0 and every segment carries its level's: a segment rate of 0 takes the call's (dta_hip.h), so a
+        # level whose learning rate is 0 is stepped with 0 -- moments and step count advance, parameters stay -- as its own
+        # EnsembleTrainer steps it, and never with another level's rate
         t0 = self.levels[0]
-        if any(t.betas != t0.betas or t.eps != t0.eps or t.keep_grads != t0.keep_grads for t in self.levels):
-            raise RuntimeError("training_step_all: the levels' Adam settings (betas, eps, keep_grads) must agree")
         for lo in range(0, len(segs), _lib.ADAM_MAX_SEGMENTS):
             part = segs[lo:lo + _lib.ADAM_MAX_SEGMENTS]
             arr = (_lib.AdamSegment * len(part))(*part)
-            _lib.check(L.dta_adam_step_multi(len(part), arr, t0.lr, t0.betas[0], t0.betas[1], t0.eps, t0.sync.grad_scale,
+            _lib.check(L.dta_adam_step_multi(len(part), arr, 0.0, t0.betas[0], t0.betas[1], t0.eps, t0.sync.grad_scale,
                                              0 if t0.keep_grads else 1, st), "dta_adam_step_multi")
         self._live = live      # inputs and labels stay referenced until the step's launches are enqueued
         return [t.loss for t in self.levels]

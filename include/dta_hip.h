@@ -319,7 +319,9 @@ typedef struct dta_adam_segment {
   const float* active; const int* dev_step; int* dev_step_next;   /* gated form, or all NULL */
   int step;                                                        /* host step count (ungated form) */
   float lr;                                                        /* > 0: this segment's learning rate instead of the call's (one Adam per
-                                                                      level, reference multi_stage.py:258-262); 0: the call's */
+                                                                      level, reference multi_stage.py:258-262); 0: the call's.  A segment
+                                                                      cannot ask for rate 0 by itself: a caller with a frozen segment
+                                                                      passes lr = 0 to the call and a rate > 0 in every stepped segment */
 } dta_adam_segment;
 int dta_adam_step_multi(int nseg, const dta_adam_segment* segs, float lr, float beta1, float beta2, float eps, float grad_scale,
                         int zero_grad, void* stream);
