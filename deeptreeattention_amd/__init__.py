@@ -13,6 +13,9 @@ The package mirrors the reference's module names for this path only:
                                      the confusion resampling of that count (every iteration in one launch)
     deeptreeattention_amd.canopy     <->  src/CHM.py + src/predict.py find_crowns: the 99th-percentile canopy height of every
                                      crown box of a resident CHM raster and the height rules on it (one launch pair)
+    deeptreeattention_amd.dead       <->  src/models/dead.py + src/predict.py predict_tile(filter_dead=True): the normalised,
+                                     resized RGB crop of every crown box from a resident uint8 raster (one launch), the
+                                     alive/dead score of the classifier's logits, and the rule that blanks dead crowns
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

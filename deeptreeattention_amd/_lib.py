@@ -93,6 +93,9 @@ class HierarchyTable(C.Structure):  # dta_hierarchy
 ADAM_MAX_SEGMENTS = 16   # DTA_ADAM_MAX_SEGMENTS
 ABUNDANCE_MAX_SPECIES = 256   # DTA_ABUNDANCE_MAX_SPECIES
 CROWN_WAVE_CELLS = 1024   # DTA_CROWN_WAVE_CELLS
+ELEM_F32, ELEM_BF16, ELEM_F16 = 0, 1, 2   # DTA_ELEM_*
+RGB_CROPS_MAX_GROUPS = 1024   # DTA_RGB_CROPS_MAX_GROUPS
+RGB_CROPS_MAX_SIZE = 512   # DTA_RGB_CROPS_MAX_SIZE
 
 
 class HeightRule(C.Structure):      # dta_height_rule
@@ -346,6 +349,12 @@ def lib():
         L.dta_crown_height.restype = C.c_int
         L.dta_crown_height.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, C.c_float, C.c_float, vp, C.POINTER(HeightRule),
                                        vp, vp, vp, vp]
+        # alive/dead crown filter: RGB crops resized on the device, and the score (dead.hip)
+        L.dta_rgb_crops.restype = C.c_int
+        L.dta_rgb_crops.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, C.c_int, C.c_int, c_float_p, c_float_p,
+                                    C.c_int, C.c_int, vp, vp, vp]
+        L.dta_dead_head.restype = C.c_int
+        L.dta_dead_head.argtypes = [vp, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

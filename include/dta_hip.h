@@ -862,6 +862,42 @@ int dta_crown_height(const float* chm, int height, int width, const int* boxes, 
                      const double* field_height, const dta_height_rule* rule, float* out_height, int* out_count,
                      unsigned char* out_keep, void* stream);
 
+/* ---- Alive/dead crown filter: the data preparation in front of the reference's alive/dead classifier and the score behind
+ * it (src/models/dead.py: utm_dataset.__getitem__ -- the crown's box plus one metre read from the RGB tile, ToTensor,
+ * Normalize, Resize([224, 224]) per crown on a CPU worker; predict_dead -- label = argmax, score = max of
+ * softmax(sigmoid(logits))).  The classifier itself is the caller's network between the two calls.
+ *
+ * Crops.  raster: uint8 [channels][height][width] on the device, 1 to 4 channels.  boxes: int32 [n][4] = (row0, col0, row1,
+ * col1), half-open, any int32 values.  Per crown: the box is grown by `pad` pixels on every side and clipped to the raster
+ * (origin (r0, c0), h rows, w columns); with S = size, every operation in float32 and rounded on its own, except the source
+ * position sy * (i + 0.5) - 0.5, which is one fused multiply-add (as torch's CPU interpolate computes it):
+ *   p(c, y, x) = (float(raster[c][r0 + y][c0 + x]) / 255 - mean[c]) / std[c]
+ *   sy = float(h) / float(S);  fy = max(sy * (i + 0.5) - 0.5, 0);  y0 = min(int(fy), h - 1);  y1 = min(y0 + 1, h - 1);  ly = fy - y0
+ *   (the same for the columns: sx, fx, x0, x1, lx)
+ *   out(c, i, j) = (1 - ly) * ((1 - lx) * p(c,y0,x0) + lx * p(c,y0,x1)) + ly * ((1 - lx) * p(c,y1,x0) + lx * p(c,y1,x1))
+ * which is bilinear interpolation with align_corners = False and no antialiasing, also where the box is larger than S x S
+ * (deeptreeattention_amd/dead.py: crops_np is the definition).  out: [n][channels][S][S] of `dtype` (one rounding of the
+ * float32 result for the 16-bit types), in that order in memory, or as [n][S][S][channels] when channels_last != 0.
+ * out_valid: 0 / 1 bytes [n]: 0 for a box with row1 <= row0 or col1 <= col0 and for one whose grown box misses the raster;
+ * such a crown's outputs are zeros.  Every output element is overwritten.  One launch of at most DTA_RGB_CROPS_MAX_GROUPS
+ * workgroups, no workspace, no atomics.  mean, std: HOST arrays of `channels` floats.  Refused on the host, before any
+ * launch: a null pointer, n < 1 or over int32, channels outside 1..4, height or width < 1, channels * height * width over
+ * int32, size outside 1..DTA_RGB_CROPS_MAX_SIZE, pad < 0, an unknown dtype, a zero std, a NaN mean or std, an out pointer
+ * that is not aligned to its element. */
+enum { DTA_ELEM_F32 = 0, DTA_ELEM_BF16 = 1, DTA_ELEM_F16 = 2 };
+#define DTA_RGB_CROPS_MAX_GROUPS 1024
+#define DTA_RGB_CROPS_MAX_SIZE 512
+int dta_rgb_crops(const unsigned char* raster, int channels, int height, int width, const int* boxes, long long n, int size,
+                  int pad, const float* mean, const float* std, int dtype, int channels_last, void* out,
+                  unsigned char* out_valid, void* stream);
+/* The score.  logits: [rows][2] of `dtype` (DTA_ELEM_*) on the device, the classifier's output for one batch.  In float32:
+ * s = 1 / (1 + exp(-logit));  p = softmax(s) over the two classes;  out_score[offset + r] = max(p),
+ * out_label[offset + r] = 1 if p[1] > p[0] else 0 (a tie is 0, as np.argmax).  offset: where the batch starts in the result
+ * arrays of the whole tile, so a driver writes every batch straight into them.  One launch.  Refused before it: a null
+ * pointer, rows < 1, offset < 0, an unknown dtype. */
+int dta_dead_head(const void* logits, int dtype, long long rows, long long offset, long long* out_label, float* out_score,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
