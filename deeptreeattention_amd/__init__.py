@@ -16,6 +16,9 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.dead       <->  src/models/dead.py + src/predict.py predict_tile(filter_dead=True): the normalised,
                                      resized RGB crop of every crown box from a resident uint8 raster (one launch), the
                                      alive/dead score of the classifier's logits, and the rule that blanks dead crowns
+    deeptreeattention_amd.reflectance  <->  src/Hyperspectral.py:138-219 generate_raster / calc_clip_index: the band mask, the
+                                     clip window and the band-first transpose between a pixel-interleaved reflectance cube
+                                     and the resident raster (DenseRaster.from_reflectance: one launch per strip of rows)
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

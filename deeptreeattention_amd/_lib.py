@@ -96,6 +96,12 @@ CROWN_WAVE_CELLS = 1024   # DTA_CROWN_WAVE_CELLS
 ELEM_F32, ELEM_BF16, ELEM_F16 = 0, 1, 2   # DTA_ELEM_*
 RGB_CROPS_MAX_GROUPS = 1024   # DTA_RGB_CROPS_MAX_GROUPS
 RGB_CROPS_MAX_SIZE = 512   # DTA_RGB_CROPS_MAX_SIZE
+REFLECTANCE_MAX_BANDS = 1024   # DTA_REFLECTANCE_MAX_BANDS
+
+
+class ReflectanceDesc(C.Structure):     # dta_reflectance_desc
+    _fields_ = [(n, C.c_int) for n in ("bands_src", "width_src", "rows", "col0", "cols", "dtype", "tiles", "out_height",
+                                       "out_row0")]
 
 
 class HeightRule(C.Structure):      # dta_height_rule
@@ -355,6 +361,9 @@ def lib():
                                     C.c_int, C.c_int, vp, vp, vp]
         L.dta_dead_head.restype = C.c_int
         L.dta_dead_head.argtypes = [vp, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp]
+        # reflectance cube -> resident raster: band selection, window, min-max and transpose in one pass (reflectance.hip)
+        L.dta_reflectance_normalise.restype = C.c_int
+        L.dta_reflectance_normalise.argtypes = [C.POINTER(ReflectanceDesc), vp, vp, C.c_int, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

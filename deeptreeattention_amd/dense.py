@@ -8,6 +8,8 @@ the window of the preprocessed raster, bit for bit (a zero-filled out-of-bounds 
 scikit-learn's "constant" threshold).  Hence:
 
     DenseRaster          one host-to-device copy of the raw raster and ONE normalise launch (dta_raster_normalise)
+    DenseRaster.from_reflectance   the same raster straight from a pixel-interleaved reflectance cube: band selection, window,
+                         min-max and transpose in one pass per strip of rows (reflectance.py; dta_reflectance_normalise)
     window_origins       pixel boxes -> window origins + crown offsets (pure host function)
     DenseRaster.windows  origins -> the float32 batch or the first conv's bf16 tiles (dta_gather_windows[_tiles])
     predict_windows      gather -> eval forward -> softmax / top-2 per batch, no host synchronisation inside the loop;
@@ -80,6 +82,7 @@ from . import _lib
 from .preprocess import PatchTiles, out_bands, _DTYPES
 
 WINDOW = 11     # Hang et al. 2020: one 11x11 window per pixel
+_TORCH_DTYPES = {torch.float32: _lib.CROP_F32, torch.int16: _lib.CROP_I16, torch.uint8: _lib.CROP_U8}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -369,6 +372,83 @@ class DenseRaster:
             self.data = torch.empty(self.bands, Hh, Ww, dtype=torch.float32, device=dev)
         _lib.check(L.dta_raster_normalise(_lib.ptr(raw), bands_raw, Hh, Ww, clip, _DTYPES[a.dtype], int(precision == "bf16"),
                                           _lib.ptr(self.data), _lib.current_stream_ptr()), "dta_raster_normalise")
+
+    @classmethod
+    def from_reflectance(cls, cube, bands="no_water", window=None, clip=10, precision="bf16", device="cuda", strip_rows=None):
+        """The resident raster straight from a pixel-interleaved reflectance cube [H][W][B] (how a NEON tile is stored: 426
+        int16 bands per pixel), bit for bit what DenseRaster(band_first, clip, precision) gives for
+        band_first = np.moveaxis(cube[r0:r1, c0:c1][:, :, reflectance.band_index(bands, B)], 2, 0) -- without that select-and-
+        transpose on the host (reflectance.reflectance_np is the definition; dta_reflectance_normalise).  bands: "no_water"
+        (the reference's mask), "all", "false_color" or a sequence of band indices; window: (row0, col0, row1, col1),
+        half-open, e.g. from reflectance.clip_index.  cube: a host array (np.memmap and anything np.asarray takes; int16, uint8
+        and float32 are used as they are, anything else is converted to float32 per strip) uploaded in strips of `strip_rows`
+        whole rows, one launch per strip (default: as many rows as 64 MiB of raw data hold -- a bound on memory, not a tuned
+        value), or a device tensor, normalised in one launch."""
+        from . import reflectance as R
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("deeptreeattention_amd.dense runs on a ROCm device only (no CPU fallback)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if precision not in ("bf16", "fp32"):
+            raise ValueError("precision must be 'bf16' or 'fp32', got {!r}".format(precision))
+        resident = isinstance(cube, torch.Tensor) and cube.is_cuda
+        if isinstance(cube, torch.Tensor) and not resident:
+            cube = cube.detach().numpy()
+        if not resident:
+            cube = cube if isinstance(cube, np.ndarray) else np.asarray(cube)
+        if cube.ndim != 3:
+            raise ValueError("the cube must be a pixel-interleaved 3-d array [rows][cols][bands]")
+        Hs, Ws, B = (int(v) for v in cube.shape)
+        if B > R.MAX_BANDS:
+            raise ValueError("{} bands per pixel: at most {}".format(B, R.MAX_BANDS))
+        r0, c0, r1, c1 = R.window_of(cube.shape, window)
+        sel = R.selected_bands(bands, B, clip)
+        if len(sel) > R.MAX_BANDS:
+            raise ValueError("{} bands selected: at most {}".format(len(sel), R.MAX_BANDS))
+        Hh, Ww = r1 - r0, c1 - c0
+        if Hh * Ww >= 2 ** 31:
+            raise ValueError("a raster of {} x {} pixels is over int32".format(Hh, Ww))
+        self = cls.__new__(cls)
+        self.bands, self.height, self.width = len(sel), Hh, Ww
+        self.shape = (self.bands, Hh, Ww)
+        self.precision, self.device = precision, dev
+        L = _lib.lib()
+        index = torch.from_numpy(sel).to(dev, non_blocking=True)
+        if precision == "bf16":
+            self.data = torch.empty(((self.bands + 15) // 16) * Hh * Ww * 16, dtype=torch.int16, device=dev)
+        else:
+            self.data = torch.empty(self.bands, Hh, Ww, dtype=torch.float32, device=dev)
+
+        def launch(strip, code, rows, out_row0):
+            d = _lib.ReflectanceDesc(B, Ws, rows, c0, Ww, code, int(precision == "bf16"), Hh, out_row0)
+            _lib.check(L.dta_reflectance_normalise(d, _lib.ptr(strip), _lib.ptr(index), self.bands, _lib.ptr(self.data),
+                                                   _lib.current_stream_ptr()), "dta_reflectance_normalise")
+
+        if resident:
+            t = cube.detach()
+            if t.device != dev:
+                raise ValueError("the cube is on {}, the raster was asked for on {}".format(t.device, dev))
+            if t.dtype not in _TORCH_DTYPES:
+                t = t.float()
+            t = t[r0:r1].contiguous()                 # whole rows: a view of a contiguous cube
+            if t.data_ptr() % 16:
+                t = t.clone()
+            launch(t, _TORCH_DTYPES[t.dtype], Hh, 0)
+            return self
+        if strip_rows is None:
+            row_bytes = Ws * B * (cube.dtype.itemsize if cube.dtype in _DTYPES else 4)
+            strip_rows = max(1, (64 << 20) // row_bytes)
+        strip_rows = int(strip_rows)
+        if strip_rows < 1:
+            raise ValueError("strip_rows must be >= 1, got {}".format(strip_rows))
+        for r in range(r0, r1, strip_rows):
+            a = cube[r:min(r + strip_rows, r1)]
+            if a.dtype not in _DTYPES:
+                a = a.astype(np.float32)
+            strip = torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+            launch(strip, _DTYPES[a.dtype], a.shape[0], r - r0)
+        return self
 
     def float(self):
         """The normalised raster as a float32 [C][H][W] tensor (bf16 form: the bf16-rounded values)."""

@@ -898,6 +898,38 @@ int dta_rgb_crops(const unsigned char* raster, int channels, int height, int wid
 int dta_dead_head(const void* logits, int dtype, long long rows, long long offset, long long* out_label, float* out_score,
                   void* stream);
 
+/* ---- Reflectance cube to resident raster: the array work of the reference's generate_raster (src/Hyperspectral.py:152-219:
+ * band selection, window, transpose to band-first) and of load_image's preprocessing (src/utils.py:36-57) in one pass over a
+ * pixel-interleaved cube, as a NEON reflectance tile is stored ([rows][cols][426] int16).  For every pixel of the column
+ * window and every k < bands:
+ *   v[k] = float(strip[row][col0 + x][band_index[k]])
+ *   out  = dta_raster_normalise's arithmetic on v[0 .. bands) -- the same float32 roundings, the same `tiny` rule, NaNs passed
+ *          over by the min and the max -- so the result is bit for bit what dta_raster_normalise(clip = 0) gives for the
+ *          selected, transposed bands.  band_index is the caller's whole selection: a band mask with load_image's 10 + 10
+ *          clip already applied (deeptreeattention_amd/reflectance.py: reflectance_np is the definition).
+ * strip: [rows][width_src][bands_src] of `dtype` (DTA_CROP_*) on the device; band_index: int32 [bands] on the device, any
+ * order, repeats allowed, every value in [0, bands_src) (a value outside is clamped into the range, never followed).
+ * out: the WHOLE raster of out_height x cols pixels, float32 [bands][out_height][cols] (tiles == 0) or the bf16 chunk form
+ * [ceil(bands / 16)][out_height * cols][16] of dta_raster_normalise (bands past `bands` in the last chunk are zero).  The
+ * call writes the raster rows out_row0 .. out_row0 + rows - 1 and nothing else, so a tile can be taken strip by strip
+ * through a bounded raw buffer.  One launch, no workspace, no atomics; no byte outside strip[0 .. rows * width_src *
+ * bands_src) is read.  Refused on the host, before any launch: a null pointer; a size below 1, col0 < 0 or out_row0 < 0;
+ * col0 + cols > width_src; out_row0 + rows > out_height; an unknown dtype; out_height * cols >= 2^31; a strip or out that
+ * is not 16-byte aligned; bands_src or bands over DTA_REFLECTANCE_MAX_BANDS. */
+#define DTA_REFLECTANCE_MAX_BANDS 1024
+typedef struct dta_reflectance_desc {
+  int bands_src;    /* bands per pixel of the cube */
+  int width_src;    /* pixels per cube row */
+  int rows;         /* rows in this strip */
+  int col0, cols;   /* column window; cols == raster width */
+  int dtype;        /* DTA_CROP_* as dta_raster_normalise */
+  int tiles;        /* 0: float32 [C][H][W]; else bf16 [ceil(C/16)][H*W][16] */
+  int out_height;   /* rows of the whole resident raster */
+  int out_row0;     /* first raster row this strip writes */
+} dta_reflectance_desc;
+int dta_reflectance_normalise(const dta_reflectance_desc* d, const void* strip, const int* band_index, int bands, void* out,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
