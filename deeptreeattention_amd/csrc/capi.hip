@@ -1654,31 +1654,22 @@ int dta_raster_normalise(const void* raw, int bands_raw, int height, int width, 
   return launch_raster_normalise(a, dtype, (hipStream_t)stream);
 }
 
-static int gather_args(const char* who, const void* raster, int bands, int height, int width, const int* origins, int n,
-                       int size, void* out, GatherArgs* a) {
-  if (!raster || !origins || !out) { dta_set_error("%s: null argument", who); return 1; }
+// ---- windows and crops of crown boxes out of the resident raster (dense.hip): ONE argument checker and ONE years loop
+// behind the six entry points.  Each keeps its own name in the texts and its own accepted side: window 4..253, crop 1..4096.
+static int gather_args(const char* who, GatherSrc src, const void* raster, int bands, int height, int width, const int* items,
+                       int n, int size, int flip, void* out, GatherArgs* a) {
+  if (!raster || !items || !out) { dta_set_error("%s: null argument", who); return 1; }
   if (bands < 1 || height < 1 || width < 1 || n < 1) { dta_set_error("%s: bad shape: bands=%d H=%d W=%d n=%d", who, bands, height, width, n); return 1; }
-  if (size < 4 || size > 253) { dta_set_error("%s: window side %d outside 4..253 (what the networks take)", who, size); return 1; }
+  if (src == SRC_WINDOW && (size < 4 || size > 253)) { dta_set_error("%s: window side %d outside 4..253 (what the networks take)", who, size); return 1; }
+  if (src == SRC_CROP && (size < 1 || size > 4096)) { dta_set_error("%s: crop side %d outside 1..4096", who, size); return 1; }
   if (((uintptr_t)raster & 15) || ((uintptr_t)out & 15)) { dta_set_error("%s: raster and output must be 16-byte aligned", who); return 1; }
-  a->raster = raster; a->origins = origins; a->out = out; a->N = n; a->C = bands; a->H = height; a->W = width; a->S = size;
+  a->raster = raster; a->items = items; a->out = out; a->N = n; a->C = bands; a->H = height; a->W = width; a->S = size;
+  a->flip = flip != 0;
   return 0;
 }
-int dta_gather_windows(const float* raster, int bands, int height, int width, const int* origins, int n, int size,
-                       float* out, void* stream) {
-  GatherArgs a;
-  if (gather_args("dta_gather_windows", raster, bands, height, width, origins, n, size, out, &a)) return 1;
-  return launch_gather_windows(a, (hipStream_t)stream);
-}
-int dta_gather_windows_tiles(const void* raster, int bands, int height, int width, const int* origins, int n, int size,
-                             void* tiles, void* stream) {
-  GatherArgs a;
-  if (gather_args("dta_gather_windows_tiles", raster, bands, height, width, origins, n, size, tiles, &a)) return 1;
-  return launch_gather_windows_tiles(a, (hipStream_t)stream);
-}
-
-int dta_gather_windows_years(const float* const* rasters, int years, int bands, int height, int width, const int* origins,
-                             int n, int size, float* const* outs, float* flags, float* clear_next, void* stream) {
-  const char* who = "dta_gather_windows_years";
+static int gather_years(const char* who, GatherSrc src, const float* const* rasters, int years, int bands, int height, int width,
+                        const int* items, int n, int size, int flip, float* const* outs, float* flags, float* clear_next,
+                        void* stream) {
   if (!rasters || !outs || !flags || flags == clear_next) { dta_set_error("%s: null argument (or flags == clear_next)", who); return 1; }
   if (years < 1 || years > DTA_MAX_YEARS) { dta_set_error("%s: 1..%d years, not %d", who, DTA_MAX_YEARS, years); return 1; }
   static_assert(DTA_MAX_YEARS <= MAXG, "header and kernel disagree");
@@ -1687,63 +1678,51 @@ int dta_gather_windows_years(const float* const* rasters, int years, int bands, 
   int present = 0;
   for (int y = 0; y < years; ++y) {
     if (!rasters[y]) continue;
-    GatherArgs g;
-    if (gather_args(who, rasters[y], bands, height, width, origins, n, size, outs[y], &g)) return 1;
-    a.g = g; a.rasters[y] = rasters[y]; a.outs[y] = outs[y];
+    if (gather_args(who, src, rasters[y], bands, height, width, items, n, size, flip, outs[y], &a.g)) return 1;
+    a.rasters[y] = rasters[y]; a.outs[y] = outs[y];
     ++present;
   }
   if (!present) { dta_set_error("%s: every year is missing: nothing to gather", who); return 1; }
   a.g.raster = nullptr; a.g.out = nullptr;
   a.years = years; a.flags = flags; a.clear_next = clear_next;
-  return launch_gather_windows_years(a, (hipStream_t)stream);
+  return src == SRC_WINDOW ? launch_gather_years<SRC_WINDOW>(a, (hipStream_t)stream) : launch_gather_years<SRC_CROP>(a, (hipStream_t)stream);
 }
 
-// ---- crops of crown boxes out of the resident raster (dense.hip) ----
-static int crop_args(const char* who, const void* raster, int bands, int height, int width, const int* boxes, int n,
-                     int size, void* out, int flip, bool tiles, CropGatherArgs* a) {
-  if (!raster || !boxes || !out) { dta_set_error("%s: null argument", who); return 1; }
-  if (bands < 1 || height < 1 || width < 1 || n < 1) { dta_set_error("%s: bad shape: bands=%d H=%d W=%d n=%d", who, bands, height, width, n); return 1; }
-  if (size < 1 || size > 4096) { dta_set_error("%s: crop side %d outside 1..4096", who, size); return 1; }
-  if (((uintptr_t)raster & 15) || ((uintptr_t)out & 15)) { dta_set_error("%s: raster and output must be 16-byte aligned", who); return 1; }
-  // one lane per 16 bytes of output: four floats of the flat batch, or half a (crop, chunk, pixel) element of the tiles
-  const size_t lanes = tiles ? (size_t)n * ((bands + 15) / 16) * size * size * 2 : ((size_t)n * bands * size * size + 3) / 4;
-  if ((lanes + 255) / 256 > 0x7FFFFFFFull) { dta_set_error("%s: batch too large for one launch", who); return 1; }
-  a->raster = raster; a->boxes = boxes; a->out = out; a->N = n; a->C = bands; a->H = height; a->W = width; a->S = size;
-  a->flip = flip != 0;
-  return 0;
+int dta_gather_windows(const float* raster, int bands, int height, int width, const int* origins, int n, int size,
+                       float* out, void* stream) {
+  GatherArgs a;
+  if (gather_args("dta_gather_windows", SRC_WINDOW, raster, bands, height, width, origins, n, size, 0, out, &a)) return 1;
+  return launch_gather<SRC_WINDOW>(a, (hipStream_t)stream);
+}
+int dta_gather_windows_tiles(const void* raster, int bands, int height, int width, const int* origins, int n, int size,
+                             void* tiles, void* stream) {
+  GatherArgs a;
+  if (gather_args("dta_gather_windows_tiles", SRC_WINDOW, raster, bands, height, width, origins, n, size, 0, tiles, &a)) return 1;
+  return launch_gather_tiles<SRC_WINDOW>(a, (hipStream_t)stream);
+}
+int dta_gather_windows_years(const float* const* rasters, int years, int bands, int height, int width, const int* origins,
+                             int n, int size, float* const* outs, float* flags, float* clear_next, void* stream) {
+  return gather_years("dta_gather_windows_years", SRC_WINDOW, rasters, years, bands, height, width, origins, n, size, 0, outs,
+                                  flags, clear_next, stream);
 }
 int dta_gather_crops(const float* raster, int bands, int height, int width, const int* boxes, int n, int size, int flip,
                      float* out, void* stream) {
-  CropGatherArgs a;
-  if (crop_args("dta_gather_crops", raster, bands, height, width, boxes, n, size, out, flip, false, &a)) return 1;
-  return launch_gather_crops(a, (hipStream_t)stream);
+  GatherArgs a;
+  if (gather_args("dta_gather_crops", SRC_CROP, raster, bands, height, width, boxes, n, size, flip, out, &a)) return 1;
+  return launch_gather<SRC_CROP>(a, (hipStream_t)stream);
 }
 int dta_gather_crops_tiles(const void* raster, int bands, int height, int width, const int* boxes, int n, int size, int flip,
                            void* tiles, void* stream) {
-  CropGatherArgs a;
-  if (crop_args("dta_gather_crops_tiles", raster, bands, height, width, boxes, n, size, tiles, flip, true, &a)) return 1;
-  return launch_gather_crops_tiles(a, (hipStream_t)stream);
+  GatherArgs a;
+  if (gather_args("dta_gather_crops_tiles", SRC_CROP, raster, bands, height, width, boxes, n, size, flip, tiles, &a)) return 1;
+  return launch_gather_tiles<SRC_CROP>(a, (hipStream_t)stream);
 }
 int dta_gather_crops_years(const float* const* rasters, int years, int bands, int height, int width, const int* boxes,
                            int n, int size, int flip, float* const* outs, float* flags, float* clear_next, void* stream) {
-  const char* who = "dta_gather_crops_years";
-  if (!rasters || !outs || !flags || flags == clear_next) { dta_set_error("%s: null argument (or flags == clear_next)", who); return 1; }
-  if (years < 1 || years > DTA_MAX_YEARS) { dta_set_error("%s: 1..%d years, not %d", who, DTA_MAX_YEARS, years); return 1; }
-  CropGatherYearsArgs a;
-  memset(&a, 0, sizeof(a));
-  int present = 0;
-  for (int y = 0; y < years; ++y) {
-    if (!rasters[y]) continue;
-    CropGatherArgs g;
-    if (crop_args(who, rasters[y], bands, height, width, boxes, n, size, outs[y], flip, false, &g)) return 1;
-    a.g = g; a.rasters[y] = rasters[y]; a.outs[y] = outs[y];
-    ++present;
-  }
-  if (!present) { dta_set_error("%s: every year is missing: nothing to gather", who); return 1; }
-  a.g.raster = nullptr; a.g.out = nullptr;
-  a.years = years; a.flags = flags; a.clear_next = clear_next;
-  return launch_gather_crops_years(a, (hipStream_t)stream);
+  return gather_years("dta_gather_crops_years", SRC_CROP, rasters, years, bands, height, width, boxes, n, size, flip, outs,
+                                flags, clear_next, stream);
 }
+
 
 int dta_crown_resolve(int levels, const float* const* probs, const long long* offsets, int n_crowns,
                       const dta_hierarchy* table, float* const* mean, long long* const* top_idx, float* const* top_score,

@@ -149,9 +149,11 @@ __device__ __forceinline__ float block_sum256(float v, float* scratch) {
   return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
-// The scaling arithmetic of the per-pixel min-max (k_preprocess_crops*, preprocess.hip; k_raster_normalise, dense.hip).
-// THE CONTRACT between the two files: the window of the normalised raster equals the normalised window bit for bit only
-// while both use these very definitions (and `#pragma clang fp contract(off)`); change them here, for both, or not at all.
+// The per-pixel min-max scaling, whole: k_preprocess_crops* (preprocess.hip), k_raster_normalise (dense.hip) and
+// k_reflectance_normalise (reflectance.hip) keep their own load / reduce structure and take everything that decides a bit
+// from here.  THE CONTRACT between the three files: window of the normalised raster = normalised window, crop = index
+// selection, from_reflectance = DenseRaster hold bit for bit because there is ONE definition; change it here or not at
+// all.  Each helper carries its own `fp contract(off)`: a user cannot forget the file-level pragma.
 // x * s rounded to float32 on its own: the empty asm makes the product opaque, so no later add can be fused into it
 __device__ __forceinline__ float mul_rounded(float x, float s) {
   float p = x * s;
@@ -162,6 +164,39 @@ __device__ __forceinline__ float mul_rounded(float x, float s) {
 __device__ __forceinline__ float to_f(float v) { return v; }
 __device__ __forceinline__ float to_f(short v) { return (float)v; }
 __device__ __forceinline__ float to_f(unsigned char v) { return (float)v; }
+// scale and offset of a pixel whose bands span lo .. hi, scikit-learn's float32 MinMaxScaler step by step
+__device__ __forceinline__ void minmax_scale(float lo, float hi, float* s, float* m) {
+#pragma clang fp contract(off)
+  const float tiny = 10.f * 1.1920928955078125e-07f;   // scikit-learn: ranges below 10 * eps(float32) are "constant"
+  float rng = hi - lo;
+  if (rng < tiny) rng = 1.f;
+  *s = 1.f / rng;
+  *m = 0.f - mul_rounded(lo, *s);
+}
+// a band's scaled value: the multiply and the add rounded SEPARATELY, as NumPy's `X *= scale; X += min` does.  (s and m
+// by reference: a kernel that keeps them in LDS reads m behind the product, not in front of mul_rounded's asm, which the
+// scheduler treats as a barrier -- read in front of it, k_preprocess_crops' four loads in flight become one)
+__device__ __forceinline__ float minmax_apply(float v, const float& s, const float& m) {
+#pragma clang fp contract(off)
+  return mul_rounded(v, s) + m;
+}
+// chunk `ch` (bands 16 ch .. 16 ch + 15) of one pixel of the bf16 chunk form out[chunk][P][16]: the scaled values rounded
+// to bf16 (nearest even), bands past C zero, two 16-byte stores.  band(c): the raw value of band c as float32,
+// asked for only while that band is below C -- each kernel keeps its own load pattern.
+template <typename F>
+__device__ __forceinline__ void minmax_store_chunk(unsigned short* out, size_t P, size_t pixel, int ch, int C, float s, float m, F band) {
+  unsigned pk[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int c = ch * 16 + 2 * e;
+    const float v0 = c < C ? minmax_apply(band(c), s, m) : 0.f;
+    const float v1 = c + 1 < C ? minmax_apply(band(c + 1), s, m) : 0.f;
+    pk[e] = pack2_fmt(v0, v1, FMT_BF16);
+  }
+  u32x4* dst = reinterpret_cast<u32x4*>(out + ((size_t)ch * P + pixel) * 16);
+  dst[0] = u32x4{pk[0], pk[1], pk[2], pk[3]};
+  dst[1] = u32x4{pk[4], pk[5], pk[6], pk[7]};
+}
 
 // ATen's nearest-neighbour source index (what torchvision's NEAREST resize dispatches to):
 // min(floor(dst * float(in / out)), in - 1).  ONE definition for k_preprocess_crops* (preprocess.hip) and the crop gathers

@@ -3,20 +3,24 @@
 // pixel position (drop bands, min-max over the bands of that pixel, src/utils.py:36-57) and an SxS window resized to SxS
 // with NEAREST is the identity, so the preprocessed window IS the window of the preprocessed raster:
 //   k_raster_normalise  the raw raster once -> the resident normalised raster (float32 planes, or bf16 channel chunks)
-//   k_gather_windows    N window origins -> the float32 NCHW batch / the first conv's bf16 tiles (pure copies, zero fill)
+//   k_gather[_tiles]<SRC_WINDOW>  N window origins -> the float32 NCHW batch / the first conv's bf16 tiles (pure copies, zero
+//                                 fill); launches and errors are named k_gather_windows[_tiles]
 //   k_crown_reduce      per-window softmax rows, grouped by crown -> mean vector, its top-2 and the window count
 // and for a multi-stage model (levels x years networks on the same windows, engine.MultiStagePredictor):
-//   k_gather_windows_years  one batch of windows out of every year's raster in ONE launch, with the years' 0/1 flags
+//   k_gather_years<SRC_WINDOW>  one batch of windows out of every year's raster in ONE launch, with the years' 0/1 flags
+//                               (k_gather_windows_years)
 //   k_crown_resolve         every level's per-crown mean and top-2, the hierarchy walk on them and the crown's window votes
 // and for the reference's production path (one crop per crown box, resized to SxS with NEAREST; src/patches.py:5-30):
-//   k_gather_crops[_tiles|_years]  N boxes -> the resized crops, an index selection from the resident raster
+//   k_gather[_tiles|_years]<SRC_CROP>  N boxes -> the resized crops, an index selection from the resident raster: the SAME
+//                                      three kernels with another source policy (k_gather_crops[_tiles|_years])
 // All are bandwidth-bound copies or short reductions: no float atomics, fixed summation order, bit-identical reruns.
 #include "../../include/dta_hip.h"
 #include "kernels.h"
 #include "walk_dev.h"
 
-// k_raster_normalise repeats k_preprocess_crops' arithmetic (preprocess.hip) through the same mul_rounded / to_f
-// (common.h): the multiply and the add of the scaling are rounded SEPARATELY, as NumPy's `X *= scale; X += min` does
+// k_raster_normalise scales through common.h's minmax_* helpers, as k_preprocess_crops* (preprocess.hip) and
+// k_reflectance_normalise (reflectance.hip) do: the multiply and the add are rounded SEPARATELY, as NumPy's
+// `X *= scale; X += min` does
 #pragma clang fp contract(off)
 
 namespace dta {
@@ -40,152 +44,68 @@ __global__ __launch_bounds__(256) void k_raster_normalise(RasterArgs a) {
     const float v = to_f(src[(size_t)c * a.P]);
     lo = fminf(lo, v); hi = fmaxf(hi, v);             // NaNs are passed over, as nanmin / nanmax do
   }
-  const float tiny = 10.f * 1.1920928955078125e-07f;   // scikit-learn: ranges below 10 * eps(float32) are "constant"
-  float rng = hi - lo;
-  if (rng < tiny) rng = 1.f;
-  const float s = 1.f / rng;
-  const float m = 0.f - mul_rounded(lo, s);
+  float s, m;
+  minmax_scale(lo, hi, &s, &m);
   if (!TILES) {
     float* out = reinterpret_cast<float*>(a.out) + p;
 #pragma unroll 8
-    for (int c = 0; c < C; ++c) out[(size_t)c * a.P] = mul_rounded(to_f(src[(size_t)c * a.P]), s) + m;
+    for (int c = 0; c < C; ++c) out[(size_t)c * a.P] = minmax_apply(to_f(src[(size_t)c * a.P]), s, m);
   } else {
     const int NC = (C + 15) / 16;
     unsigned short* out = reinterpret_cast<unsigned short*>(a.out);
-    for (int ch = 0; ch < NC; ++ch) {
-      unsigned pk[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int c = ch * 16 + 2 * e;
-        const float v0 = c < C ? mul_rounded(to_f(src[(size_t)c * a.P]), s) + m : 0.f;
-        const float v1 = c + 1 < C ? mul_rounded(to_f(src[(size_t)(c + 1) * a.P]), s) + m : 0.f;
-        pk[e] = pack2_fmt(v0, v1, FMT_BF16);
-      }
-      u32x4* dst = reinterpret_cast<u32x4*>(out + ((size_t)ch * a.P + p) * 16);
-      dst[0] = u32x4{pk[0], pk[1], pk[2], pk[3]};
-      dst[1] = u32x4{pk[4], pk[5], pk[6], pk[7]};
-    }
+    for (int ch = 0; ch < NC; ++ch)
+      minmax_store_chunk(out, (size_t)a.P, (size_t)p, ch, C, s, m, [&](int c) { return to_f(src[(size_t)c * a.P]); });
   }
 }
 
-// float32 NCHW batch [N][C][S][S] out of the float32 raster [C][H][W].  The batch is one flat array; a lane owns four
-// consecutive elements of it (one 16-byte store; a window's C*S*S floats are not a multiple of four, so a lane's four
-// may straddle rows, planes or windows: the index is decomposed once and carried).  Positions outside the raster: 0.
-// (ONE definition for k_gather_windows and k_gather_windows_years: the same lane writes the same bytes in both.)
-// Returns whether any of the lane's elements is non-zero (NaN counts as non-zero).
-__device__ __forceinline__ bool gather_lane(const GatherArgs& a, size_t q4) {
-  const size_t total = (size_t)a.N * a.C * a.S * a.S;
-  size_t e = q4 * 4;
-  if (e >= total) return false;
-  const int S = a.S, SS = S * S;
-  const size_t per = (size_t)a.C * SS;
-  int n = (int)(e / per);
-  int r = (int)(e - (size_t)n * per);
-  int c = r / SS, q = r - c * SS;
-  int i = q / S, j = q - i * S;
-  const float* ras = reinterpret_cast<const float*>(a.raster);
-  const size_t plane = (size_t)a.H * a.W;
-  long long row0 = a.origins[2 * n], col0 = a.origins[2 * n + 1];
-  float v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[k] = 0.f;
-    if (e + k < total) {
-      const long long rr = row0 + i, cc = col0 + j;
-      if (rr >= 0 && rr < a.H && cc >= 0 && cc < a.W) v[k] = ras[(size_t)c * plane + (size_t)rr * a.W + (size_t)cc];
-      if (++j == S) {
-        j = 0;
-        if (++i == S) {
-          i = 0;
-          if (++c == a.C) {
-            c = 0; ++n;
-            if (n < a.N) { row0 = a.origins[2 * n]; col0 = a.origins[2 * n + 1]; }
-          }
-        }
-      }
-    }
+// ---- the gathers: ONE body over a compile-time source policy.  An item is a window origin or a crown box; a policy loads
+// item n and says which raster offset output pixel (i, j) of it reads, or false: nothing to read, the output is zero (a position
+// off the raster, an empty box).  Every read is guarded, whatever the item says; offsets into the raster are 64-bit.
+template <GatherSrc P> struct Src;
+// windows: output pixel (i, j) of the window at origin (row, col) is raster pixel (row + i, col + j) -- a pure copy
+template <> struct Src<SRC_WINDOW> {
+  long long row0, col0;
+  __device__ __forceinline__ Src(const GatherArgs& a, int n) : row0(a.items[2 * n]), col0(a.items[2 * n + 1]) {}
+  __device__ __forceinline__ bool at(const GatherArgs& a, int i, int j, size_t* off) const {
+    const long long rr = row0 + i, cc = col0 + j;
+    if (rr < 0 || rr >= a.H || cc < 0 || cc >= a.W) return false;
+    *off = (size_t)rr * a.W + (size_t)cc;
+    return true;
   }
-  float* out = reinterpret_cast<float*>(a.out);
-  if (e + 4 <= total) *reinterpret_cast<f32x4*>(out + e) = f32x4{v[0], v[1], v[2], v[3]};
-  else for (int k = 0; e + k < total; ++k) out[e + k] = v[k];
-  return !(v[0] == 0.f && v[1] == 0.f && v[2] == 0.f && v[3] == 0.f);
-}
-__global__ __launch_bounds__(256) void k_gather_windows(GatherArgs a) {
-  gather_lane(a, (size_t)blockIdx.x * 256 + threadIdx.x);
-}
-
-// The same batch of windows out of every year's raster of an ensemble: blockIdx.y = year, every year the lanes and bytes of
-// k_gather_windows.  A year without a raster (NULL) writes nothing: its batch is the caller's persistent zero buffer.
-// flags[y] = 1 when year y's batch has a non-zero element (NaN counts), else it stays 0 -- what k_year_flags (heads.hip)
-// says after reading the finished batch back, here from the values on their way out: a wave that wrote a non-zero element
-// stores 1.f once (plain stores of one value: no atomics, any order).  flags arrive zeroed; clear_next is the bank the
-// NEXT call sets (dta_year_flags' protocol).
-__global__ __launch_bounds__(256) void k_gather_windows_years(GatherYearsArgs a) {
-  const int y = blockIdx.y;
-  if (a.clear_next && blockIdx.x == 0 && threadIdx.x == 0) a.clear_next[y] = 0.f;
-  if (!a.rasters[y]) return;
-  GatherArgs g = a.g;
-  g.raster = a.rasters[y]; g.out = a.outs[y];
-  const bool hit = gather_lane(g, (size_t)blockIdx.x * 256 + threadIdx.x);
-  const bool any = __any(hit);
-  if (any && (threadIdx.x & 63) == 0) a.flags[y] = 1.f;
-}
-
-// The first conv's bf16 tiles [N][NC][S*S][16] (preprocess.PatchTiles) out of the bf16 raster [NC][P][16]: an element
-// (window, chunk, pixel) is a 32-byte copy; a lane moves one 16-byte half of it, consecutive lanes consecutive halves, so
-// the stores of a wave are one contiguous run and its loads runs of S pixels (32 * S bytes) of a raster row.
-__global__ __launch_bounds__(256) void k_gather_windows_tiles(GatherArgs a) {
-  const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const int S = a.S, SS = S * S, NC = (a.C + 15) / 16;
-  const size_t total = (size_t)a.N * NC * SS * 2;
-  if (id >= total) return;
-  const int half = (int)(id & 1);
-  const size_t el = id >> 1;
-  const int q = (int)(el % SS);
-  const size_t t = el / SS;
-  const int ch = (int)(t % NC), n = (int)(t / NC);
-  const int i = q / S, j = q - i * S;
-  const long long rr = (long long)a.origins[2 * n] + i, cc = (long long)a.origins[2 * n + 1] + j;
-  u32x4 v = u32x4{0u, 0u, 0u, 0u};
-  if (rr >= 0 && rr < a.H && cc >= 0 && cc < a.W) {
-    const size_t plane = (size_t)a.H * a.W;
-    v = reinterpret_cast<const u32x4*>(a.raster)[((size_t)ch * plane + (size_t)rr * a.W + (size_t)cc) * 2 + half];
-  }
-  reinterpret_cast<u32x4*>(a.out)[id] = v;
-}
-
-// ---- crops: a crown's box cut out of the raster and resized to S x S with NEAREST (reference src/patches.py:5-30 `crop`,
+};
+// crops: a crown's box cut out of the raster and resized to S x S with NEAREST (reference src/patches.py:5-30 `crop`,
 // src/utils.py:59-79 `load_image`).  The normalisation is per pixel position and a NEAREST resize only selects pixels, so
 // the resized, preprocessed crop of a box is an index selection from the normalised raster: output pixel (i, j) reads
 // raster pixel (row0 + nearest_src(i, h, S), col0 + nearest_src(j, w, S)) -- nearest_src (common.h) is the very function
 // k_preprocess_crops resizes with, which is what makes the two bit-identical.  flip: output (i, j) takes the resized
 // pixel (S - 1 - i, S - 1 - j), both training flips (src/augmentation.py:13-14), as k_preprocess_crops applies them.
-// A box with no rows or no columns: an all-zero crop (the dataset's fill for a missing crop, data.py:295-296).  Every
-// read is guarded: a source position outside the raster reads 0, whatever the box says; offsets into the raster 64-bit.
-struct CropBox { long long row0, col0; int h, w; float sh, sw; };
-__device__ __forceinline__ CropBox crop_box(const int* boxes, int n, int S) {
-  const int* b = boxes + (size_t)n * 4;
-  const int r0 = b[0], c0 = b[1], r1 = b[2], c1 = b[3];
-  CropBox x;
-  x.row0 = r0; x.col0 = c0;
-  x.h = (int)((unsigned)r1 - (unsigned)r0); x.w = (int)((unsigned)c1 - (unsigned)c0);      // (a side past 2^31 wraps: guarded reads)
-  x.sh = nearest_scale(x.h, S); x.sw = nearest_scale(x.w, S);
-  return x;
-}
-// the raster offset output pixel (i, j) of box b reads, or -1: nothing to read (an empty box, a position off the raster)
-__device__ __forceinline__ long long crop_src(const CropBox& b, int i, int j, int S, int flip, int H, int W) {
-  if (b.h <= 0 || b.w <= 0) return -1;
-  if (flip) { i = S - 1 - i; j = S - 1 - j; }
-  const long long rr = b.row0 + nearest_at(i, b.sh, b.h), cc = b.col0 + nearest_at(j, b.sw, b.w);
-  if (rr < 0 || rr >= H || cc < 0 || cc >= W) return -1;
-  return rr * W + cc;
-}
+// A box with no rows or no columns: an all-zero crop (the dataset's fill for a missing crop, data.py:295-296).
+template <> struct Src<SRC_CROP> {
+  long long row0, col0; int h, w; float sh, sw;
+  __device__ __forceinline__ Src(const GatherArgs& a, int n) {
+    const int* b = a.items + (size_t)n * 4;
+    const int r0 = b[0], c0 = b[1], r1 = b[2], c1 = b[3];
+    row0 = r0; col0 = c0;
+    h = (int)((unsigned)r1 - (unsigned)r0); w = (int)((unsigned)c1 - (unsigned)c0);      // (a side past 2^31 wraps: guarded reads)
+    sh = nearest_scale(h, a.S); sw = nearest_scale(w, a.S);
+  }
+  __device__ __forceinline__ bool at(const GatherArgs& a, int i, int j, size_t* off) const {
+    if (h <= 0 || w <= 0) return false;
+    if (a.flip) { i = a.S - 1 - i; j = a.S - 1 - j; }
+    const long long rr = row0 + nearest_at(i, sh, h), cc = col0 + nearest_at(j, sw, w);
+    if (rr < 0 || rr >= a.H || cc < 0 || cc >= a.W) return false;
+    *off = (size_t)rr * a.W + (size_t)cc;
+    return true;
+  }
+};
 
-// float32 NCHW batch [N][C][S][S]: gather_lane's scheme -- a lane owns four consecutive floats of the flat batch and does
-// one 16-byte store; its four may straddle rows, planes and crops, and a lane that steps into the next crop reloads that
-// crop's box.  (ONE definition for k_gather_crops and k_gather_crops_years.)  Returns whether any of the lane's elements
-// is non-zero (NaN counts as non-zero).
-__device__ __forceinline__ bool crop_lane(const CropGatherArgs& a, size_t q4) {
+// float32 NCHW batch [N][C][S][S] out of the float32 raster [C][H][W].  The batch is one flat array; a lane owns four
+// consecutive elements of it (one 16-byte store; an item's C*S*S floats are not a multiple of four, so a lane's four may
+// straddle rows, planes or items: the index is decomposed once and carried, and a lane that steps into the next item
+// loads that item).  The same lane writes the same bytes in k_gather and k_gather_years.
+// Returns whether any of the lane's elements is non-zero (NaN counts as non-zero).
+template <GatherSrc P>
+__device__ __forceinline__ bool gather_lane(const GatherArgs& a, size_t q4) {
   const size_t total = (size_t)a.N * a.C * a.S * a.S;
   const size_t e = q4 * 4;
   if (e >= total) return false;
@@ -197,21 +117,21 @@ __device__ __forceinline__ bool crop_lane(const CropGatherArgs& a, size_t q4) {
   int i = q / S, j = q - i * S;
   const float* ras = reinterpret_cast<const float*>(a.raster);
   const size_t plane = (size_t)a.H * a.W;
-  CropBox b = crop_box(a.boxes, n, S);
+  Src<P> it(a, n);
   float v[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     v[k] = 0.f;
     if (e + k < total) {
-      const long long src = crop_src(b, i, j, S, a.flip, a.H, a.W);
-      if (src >= 0) v[k] = ras[(size_t)c * plane + (size_t)src];
+      size_t src;
+      if (it.at(a, i, j, &src)) v[k] = ras[(size_t)c * plane + src];
       if (++j == S) {
         j = 0;
         if (++i == S) {
           i = 0;
           if (++c == a.C) {
             c = 0; ++n;
-            if (n < a.N) b = crop_box(a.boxes, n, S);
+            if (n < a.N) it = Src<P>(a, n);
           }
         }
       }
@@ -222,27 +142,35 @@ __device__ __forceinline__ bool crop_lane(const CropGatherArgs& a, size_t q4) {
   else for (int k = 0; e + k < total; ++k) out[e + k] = v[k];
   return !(v[0] == 0.f && v[1] == 0.f && v[2] == 0.f && v[3] == 0.f);
 }
-__global__ __launch_bounds__(256) void k_gather_crops(CropGatherArgs a) {
-  crop_lane(a, (size_t)blockIdx.x * 256 + threadIdx.x);
+template <GatherSrc P>
+__global__ __launch_bounds__(256) void k_gather(GatherArgs a) {
+  gather_lane<P>(a, (size_t)blockIdx.x * 256 + threadIdx.x);
 }
 
-// The same boxes out of every year's raster: blockIdx.y = year, every year the lanes and bytes of k_gather_crops; a missing
-// year (NULL) writes nothing.  flags / clear_next: k_gather_windows_years' protocol, word for word.
-__global__ __launch_bounds__(256) void k_gather_crops_years(CropGatherYearsArgs a) {
+// The same batch of items out of every year's raster of an ensemble: blockIdx.y = year, every year the lanes and bytes of
+// k_gather.  A year without a raster (NULL) writes nothing: its batch is the caller's persistent zero buffer.
+// flags[y] = 1 when year y's batch has a non-zero element (NaN counts), else it stays 0 -- what k_year_flags (heads.hip)
+// says after reading the finished batch back, here from the values on their way out: a wave that wrote a non-zero element
+// stores 1.f once (plain stores of one value: no atomics, any order).  flags arrive zeroed; clear_next is the bank the
+// NEXT call sets (dta_year_flags' protocol).
+template <GatherSrc P>
+__global__ __launch_bounds__(256) void k_gather_years(GatherYearsArgs a) {
   const int y = blockIdx.y;
   if (a.clear_next && blockIdx.x == 0 && threadIdx.x == 0) a.clear_next[y] = 0.f;
   if (!a.rasters[y]) return;
-  CropGatherArgs g = a.g;
+  GatherArgs g = a.g;
   g.raster = a.rasters[y]; g.out = a.outs[y];
-  const bool hit = crop_lane(g, (size_t)blockIdx.x * 256 + threadIdx.x);
+  const bool hit = gather_lane<P>(g, (size_t)blockIdx.x * 256 + threadIdx.x);
   const bool any = __any(hit);
   if (any && (threadIdx.x & 63) == 0) a.flags[y] = 1.f;
 }
 
-// The first conv's bf16 tiles [N][NC][S*S][16] out of the bf16 raster [NC][P][16], as k_gather_windows_tiles: a lane moves
-// one 16-byte half of a (crop, chunk, pixel) element, consecutive lanes consecutive halves -- the stores of a wave are one
-// contiguous run, its loads the selected pixels of the box's rows (an upsampled box: the same 32 bytes several times).
-__global__ __launch_bounds__(256) void k_gather_crops_tiles(CropGatherArgs a) {
+// The first conv's bf16 tiles [N][NC][S*S][16] (preprocess.PatchTiles) out of the bf16 raster [NC][P][16]: an element
+// (item, chunk, pixel) is a 32-byte copy; a lane moves one 16-byte half of it, consecutive lanes consecutive halves, so
+// the stores of a wave are one contiguous run and its loads runs of S pixels (32 * S bytes) of a raster row for a window,
+// the selected pixels of the box's rows for a crop (an upsampled box: the same 32 bytes several times).
+template <GatherSrc P>
+__global__ __launch_bounds__(256) void k_gather_tiles(GatherArgs a) {
   const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
   const int S = a.S, SS = S * S, NC = (a.C + 15) / 16;
   const size_t total = (size_t)a.N * NC * SS * 2;
@@ -253,14 +181,15 @@ __global__ __launch_bounds__(256) void k_gather_crops_tiles(CropGatherArgs a) {
   const size_t t = el / SS;
   const int ch = (int)(t % NC), n = (int)(t / NC);
   const int i = q / S, j = q - i * S;
-  const long long src = crop_src(crop_box(a.boxes, n, S), i, j, S, a.flip, a.H, a.W);
   u32x4 v = u32x4{0u, 0u, 0u, 0u};
-  if (src >= 0) {
+  size_t src;
+  if (Src<P>(a, n).at(a, i, j, &src)) {
     const size_t plane = (size_t)a.H * a.W;
-    v = reinterpret_cast<const u32x4*>(a.raster)[((size_t)ch * plane + (size_t)src) * 2 + half];
+    v = reinterpret_cast<const u32x4*>(a.raster)[((size_t)ch * plane + src) * 2 + half];
   }
   reinterpret_cast<u32x4*>(a.out)[id] = v;
 }
+
 
 // One workgroup per crown.  A thread owns classes t, t + 256, ...: it adds the crown's rows of that class in row order
 // (one float32 accumulator, no atomics, no tree: the order is the definition, dense.crown_reduce_np) and divides by the
@@ -420,65 +349,51 @@ int launch_raster_normalise(const RasterArgs& a, int dtype, hipStream_t st) {
   }
 }
 
-int launch_gather_windows(const GatherArgs& a, hipStream_t st) {
+// One launcher per form.  who: the kernel's name, "k_gather_windows" ...; the C entry point's is "dta_" + who from its third
+// character on.  lanes: one per 16 bytes of output.
+template <GatherSrc P>
+int launch_gather(const GatherArgs& a, hipStream_t st) {
+  const char* who = P == SRC_WINDOW ? "k_gather_windows" : "k_gather_crops";
   const size_t total = (size_t)a.N * a.C * a.S * a.S, lanes = (total + 3) / 4;
   const size_t blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_windows: batch too large for one launch"); return 1; }
-  hipLaunchKernelGGL(k_gather_windows, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  DTA_CHECK_LAUNCH("k_gather_windows");
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_%s: batch too large for one launch", who + 2); return 1; }
+  hipLaunchKernelGGL(k_gather<P>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH(who);
   return 0;
 }
 
-int launch_gather_windows_years(const GatherYearsArgs& a, hipStream_t st) {
+template <GatherSrc P>
+int launch_gather_years(const GatherYearsArgs& a, hipStream_t st) {
+  const char* who = P == SRC_WINDOW ? "k_gather_windows_years" : "k_gather_crops_years";
   const size_t total = (size_t)a.g.N * a.g.C * a.g.S * a.g.S, lanes = (total + 3) / 4;
   const size_t blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_windows_years: batch too large for one launch"); return 1; }
-  if (a.years < 1 || a.years > MAXG) { dta_set_error("dta_gather_windows_years: 1..%d years", MAXG); return 1; }
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_%s: batch too large for one launch", who + 2); return 1; }
+  if (a.years < 1 || a.years > MAXG) { dta_set_error("dta_%s: 1..%d years", who + 2, MAXG); return 1; }
   // flags must be zero on entry: cleared here, unless the caller alternates two banks and lets each call clear the other
-  if (!a.clear_next && hipMemsetAsync(a.flags, 0, sizeof(float) * a.years, st) != hipSuccess) { dta_set_error("dta_gather_windows_years: memset failed"); return 1; }
-  hipLaunchKernelGGL(k_gather_windows_years, dim3((unsigned)blocks, a.years), dim3(256), 0, st, a);
-  DTA_CHECK_LAUNCH("k_gather_windows_years");
+  if (!a.clear_next && hipMemsetAsync(a.flags, 0, sizeof(float) * a.years, st) != hipSuccess) { dta_set_error("dta_%s: memset failed", who + 2); return 1; }
+  hipLaunchKernelGGL(k_gather_years<P>, dim3((unsigned)blocks, a.years), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH(who);
   return 0;
 }
 
-int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st) {
+template <GatherSrc P>
+int launch_gather_tiles(const GatherArgs& a, hipStream_t st) {
+  const char* who = P == SRC_WINDOW ? "k_gather_windows_tiles" : "k_gather_crops_tiles";
   const size_t total = (size_t)a.N * ((a.C + 15) / 16) * a.S * a.S * 2;
   const size_t blocks = (total + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_windows_tiles: batch too large for one launch"); return 1; }
-  hipLaunchKernelGGL(k_gather_windows_tiles, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  DTA_CHECK_LAUNCH("k_gather_windows_tiles");
+  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_%s: batch too large for one launch", who + 2); return 1; }
+  hipLaunchKernelGGL(k_gather_tiles<P>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  DTA_CHECK_LAUNCH(who);
   return 0;
 }
 
-int launch_gather_crops(const CropGatherArgs& a, hipStream_t st) {
-  const size_t total = (size_t)a.N * a.C * a.S * a.S, lanes = (total + 3) / 4;
-  const size_t blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_crops: batch too large for one launch"); return 1; }
-  hipLaunchKernelGGL(k_gather_crops, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  DTA_CHECK_LAUNCH("k_gather_crops");
-  return 0;
-}
+template int launch_gather<SRC_WINDOW>(const GatherArgs&, hipStream_t);
+template int launch_gather<SRC_CROP>(const GatherArgs&, hipStream_t);
+template int launch_gather_years<SRC_WINDOW>(const GatherYearsArgs&, hipStream_t);
+template int launch_gather_years<SRC_CROP>(const GatherYearsArgs&, hipStream_t);
+template int launch_gather_tiles<SRC_WINDOW>(const GatherArgs&, hipStream_t);
+template int launch_gather_tiles<SRC_CROP>(const GatherArgs&, hipStream_t);
 
-int launch_gather_crops_years(const CropGatherYearsArgs& a, hipStream_t st) {
-  const size_t total = (size_t)a.g.N * a.g.C * a.g.S * a.g.S, lanes = (total + 3) / 4;
-  const size_t blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_crops_years: batch too large for one launch"); return 1; }
-  if (a.years < 1 || a.years > MAXG) { dta_set_error("dta_gather_crops_years: 1..%d years", MAXG); return 1; }
-  // flags must be zero on entry: cleared here, unless the caller alternates two banks and lets each call clear the other
-  if (!a.clear_next && hipMemsetAsync(a.flags, 0, sizeof(float) * a.years, st) != hipSuccess) { dta_set_error("dta_gather_crops_years: memset failed"); return 1; }
-  hipLaunchKernelGGL(k_gather_crops_years, dim3((unsigned)blocks, a.years), dim3(256), 0, st, a);
-  DTA_CHECK_LAUNCH("k_gather_crops_years");
-  return 0;
-}
-
-int launch_gather_crops_tiles(const CropGatherArgs& a, hipStream_t st) {
-  const size_t total = (size_t)a.N * ((a.C + 15) / 16) * a.S * a.S * 2;
-  const size_t blocks = (total + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) { dta_set_error("dta_gather_crops_tiles: batch too large for one launch"); return 1; }
-  hipLaunchKernelGGL(k_gather_crops_tiles, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  DTA_CHECK_LAUNCH("k_gather_crops_tiles");
-  return 0;
-}
 
 int launch_crown_reduce(const CrownArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_crown_reduce, dim3(a.n_crowns), dim3(256), 1024 * 4, st, a);

@@ -684,27 +684,23 @@ int launch_eval_metrics_multi(const EvalMulti& m, hipStream_t st);
 // out: float32 [C][P], or (tiles) bf16 [ceil(C / 16)][P][16]
 struct RasterArgs { const void* raw; void* out; long long P; int c0, C, tiles; };
 int launch_raster_normalise(const RasterArgs& a, int dtype, hipStream_t st);      // dtype: DTA_CROP_F32 / I16 / U8
-// origins [N][2] int32 (row, col) of each window's top-left corner, anywhere (outside the raster: zeros)
-struct GatherArgs { const void* raster; const int* origins; void* out; int N, C, H, W, S; };
-int launch_gather_windows(const GatherArgs& a, hipStream_t st);          // float32 [C][H][W] -> float32 [N][C][S][S]
-int launch_gather_windows_tiles(const GatherArgs& a, hipStream_t st);    // bf16 chunks -> bf16 [N][ceil(C / 16)][S * S][16]
+// the gathers, ONE body over a compile-time source policy (dense.hip: Src<P>).  items: SRC_WINDOW origins [N][2] int32 (row,
+// col) of each window's top-left corner, output pixel (i, j) = raster pixel (row + i, col + j); SRC_CROP boxes [N][4] int32
+// (row0, col0, row1, col1), half-open, each resized to S x S with NEAREST (nearest_src, common.h), flip != 0: both flips after
+// the resize (crops only), a box with no rows or no columns an all-zero crop.  Items lie anywhere: a source position outside
+// the raster reads 0.
+enum GatherSrc { SRC_WINDOW, SRC_CROP };
+struct GatherArgs { const void* raster; const int* items; void* out; int N, C, H, W, S, flip; };
+template <GatherSrc P> int launch_gather(const GatherArgs& a, hipStream_t st);          // float32 [C][H][W] -> float32 [N][C][S][S]
+template <GatherSrc P> int launch_gather_tiles(const GatherArgs& a, hipStream_t st);    // bf16 chunks -> bf16 [N][ceil(C / 16)][S * S][16]
 // probs [rows][classes], crown k = rows offsets[k] .. offsets[k + 1]
 struct CrownArgs { const float* probs; const long long* offsets; int n_crowns, classes;
                    float* mean; long long* top_idx; float* top_score; int* count; };
 int launch_crown_reduce(const CrownArgs& a, hipStream_t st);
-// the same batch of windows (g: origins, N, C, H, W, S) out of every year's float32 raster (NULL: a missing year, nothing
+// the same batch of items (g: items, N, C, H, W, S, flip) out of every year's float32 raster (NULL: a missing year, nothing
 // written) into that year's batch, with the years' 0/1 flags (k_year_flags' meaning and bank protocol)
 struct GatherYearsArgs { const float* rasters[MAXG]; float* outs[MAXG]; GatherArgs g; int years; float* flags; float* clear_next; };
-int launch_gather_windows_years(const GatherYearsArgs& a, hipStream_t st);
-// crops: boxes [N][4] int32 (row0, col0, row1, col1), half-open, in raster pixels, anywhere; each box resized to S x S with
-// NEAREST (nearest_src, common.h), flip != 0: both flips after the resize.  A source position outside the raster reads 0;
-// a box with no rows or no columns gives an all-zero crop.  Layouts as the window gathers'.
-struct CropGatherArgs { const void* raster; const int* boxes; void* out; int N, C, H, W, S, flip; };
-int launch_gather_crops(const CropGatherArgs& a, hipStream_t st);          // float32 [C][H][W] -> float32 [N][C][S][S]
-int launch_gather_crops_tiles(const CropGatherArgs& a, hipStream_t st);    // bf16 chunks -> bf16 [N][ceil(C / 16)][S * S][16]
-// the same boxes out of every year's float32 raster: GatherYearsArgs' meaning of rasters / outs / flags / clear_next
-struct CropGatherYearsArgs { const float* rasters[MAXG]; float* outs[MAXG]; CropGatherArgs g; int years; float* flags; float* clear_next; };
-int launch_gather_crops_years(const CropGatherYearsArgs& a, hipStream_t st);
+template <GatherSrc P> int launch_gather_years(const GatherYearsArgs& a, hipStream_t st);
 // every level's per-crown mean (may be NULL) / top-2 as k_crown_reduce, the crowns' count, the walk on the levels' top-1
 // (e: table and ens_* outputs per crown; e.labels / e.confusion unused) and -- win_label / votes both or neither -- the
 // number of a crown's windows whose own label is each species: votes int32 [n_crowns][e.n_species]

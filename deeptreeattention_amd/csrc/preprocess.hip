@@ -12,7 +12,8 @@
 
 // Bit-exactness with the reference needs the multiply and the add of the scaling rounded SEPARATELY (NumPy does
 // `X *= scale; X += min`): no fused multiply-add in this file (hipcc contracts by default, and HIP's __fmul_rn /
-// __fadd_rn are plain operators that the contraction sees through; see mul_rounded in common.h).
+// __fadd_rn are plain operators that the contraction sees through).  The scaling itself -- threshold, constant-range rule,
+// offset, scaled value, chunk store -- is common.h's minmax_*: the kernels here only load and reduce.
 #pragma clang fp contract(off)
 
 namespace {
@@ -49,7 +50,6 @@ __global__ __launch_bounds__(256) void k_preprocess_crops(CropArgs a) {
     pix[p] = nearest_src(i, h, S) * w + nearest_src(j, w, S);
   }
   __syncthreads();
-  const float tiny = 10.f * 1.1920928955078125e-07f;   // scikit-learn: ranges below 10 * eps(float32) are "constant"
   if (LAYOUT == 0) {
     const size_t plane = (size_t)h * w;
     int K = 256 / a.np; if (K < 1) K = 1; if (K > 8) K = 8;
@@ -68,16 +68,13 @@ __global__ __launch_bounds__(256) void k_preprocess_crops(CropArgs a) {
     for (int p = t; p < NP; p += 256) {
       float lo = part[p], hi = part[K * a.np + p];
       for (int k = 1; k < K; ++k) { lo = fminf(lo, part[k * a.np + p]); hi = fmaxf(hi, part[(K + k) * a.np + p]); }
-      float rng = hi - lo;
-      if (rng < tiny) rng = 1.f;
-      const float s = 1.f / rng;
-      scl[p] = s; mn[p] = 0.f - mul_rounded(lo, s);
+      minmax_scale(lo, hi, &scl[p], &mn[p]);
     }
     __syncthreads();
     for (int i = t; i < C * NP; i += 256) {
       const int c = i / NP, p = i - c * NP;
       const float v = to_f(raw[(size_t)(a.c0 + c) * plane + pix[p]]);
-      out[(size_t)c * SS + p0 + p] = mul_rounded(v, scl[p]) + mn[p];
+      out[(size_t)c * SS + p0 + p] = minmax_apply(v, scl[p], mn[p]);
     }
   } else {
     const int lane = t & 63, wv = t >> 6;
@@ -99,11 +96,7 @@ __global__ __launch_bounds__(256) void k_preprocess_crops(CropArgs a) {
       }
       if (lane < 2) {
         const int p = lane ? pb : pa;
-        const float lo = lane ? lo1 : lo0, hi = lane ? hi1 : hi0;
-        float rng = hi - lo;
-        if (rng < tiny) rng = 1.f;
-        const float s = 1.f / rng;
-        scl[p] = s; mn[p] = 0.f - mul_rounded(lo, s);
+        minmax_scale(lane ? lo1 : lo0, lane ? hi1 : hi0, &scl[p], &mn[p]);
       }
     }
     __syncthreads();
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(256) void k_preprocess_crops(CropArgs a) {
             v[u] = to_f(raw[(size_t)pix[pp[u]] * a.Craw + a.c0 + cb + lane]);
           }
 #pragma unroll
-          for (int u = 0; u < 4; ++u) part[lane * pitch + pp[u]] = mul_rounded(v[u], scl[pp[u]]) + mn[pp[u]];
+          for (int u = 0; u < 4; ++u) part[lane * pitch + pp[u]] = minmax_apply(v[u], scl[pp[u]], mn[pp[u]]);
         }
       __syncthreads();
       for (int i = t; i < nc * NP; i += 256) {
@@ -160,7 +153,6 @@ __global__ __launch_bounds__(256) void k_preprocess_crops_tiles(CropArgs a, unsi
     pix[p] = nearest_src(i, h, S) * w + nearest_src(j, w, S);
   }
   __syncthreads();
-  const float tiny = 10.f * 1.1920928955078125e-07f;
   const size_t plane = (size_t)h * w;
   auto at = [&](int p, int c) -> float {
     return LAYOUT == 0 ? to_f(raw[(size_t)(a.c0 + c) * plane + pix[p]]) : to_f(raw[(size_t)pix[p] * a.Craw + a.c0 + c]);
@@ -173,29 +165,13 @@ __global__ __launch_bounds__(256) void k_preprocess_crops_tiles(CropArgs a, unsi
       for (int c = lane; c < C; c += 64) { const float v = at(p, c); lo = fminf(lo, v); hi = fmaxf(hi, v); }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o)); hi = fmaxf(hi, __shfl_xor(hi, o)); }
-      if (lane == 0) {
-        float rng = hi - lo;
-        if (rng < tiny) rng = 1.f;
-        const float s = 1.f / rng;
-        scl[p] = s; mn[p] = 0.f - mul_rounded(lo, s);
-      }
+      if (lane == 0) minmax_scale(lo, hi, &scl[p], &mn[p]);
     }
   }
   __syncthreads();
   for (int i = t; i < NC * NP; i += 256) {
     const int ch = LAYOUT == 0 ? i / NP : i % NC, p = LAYOUT == 0 ? i % NP : i / NC;   // consecutive lanes: consecutive raw bytes
-    const float s = scl[p], m = mn[p];
-    unsigned pk[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c0 = ch * 16 + 2 * e;
-      const float v0 = c0 < C ? mul_rounded(at(p, c0), s) + m : 0.f;
-      const float v1 = c0 + 1 < C ? mul_rounded(at(p, c0 + 1), s) + m : 0.f;
-      pk[e] = pack2_fmt(v0, v1, FMT_BF16);
-    }
-    u32x4* dst = reinterpret_cast<u32x4*>(out + ((size_t)ch * SS + p0 + p) * 16);
-    dst[0] = u32x4{pk[0], pk[1], pk[2], pk[3]};
-    dst[1] = u32x4{pk[4], pk[5], pk[6], pk[7]};
+    minmax_store_chunk(out, SS, p0 + p, ch, C, scl[p], mn[p], [&](int c) { return at(p, c); });
   }
 }
 

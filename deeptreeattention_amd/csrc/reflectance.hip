@@ -4,8 +4,8 @@
 // band-first (float32 planes) or chunk-first (bf16 [chunk][pixel][16]).  One pass:
 //   k_reflectance_normalise  a strip of cube rows -> its rows of the normalised raster: band selection, column window,
 //                            per-pixel min-max and the transpose, through LDS
-// The arithmetic is k_raster_normalise's (dense.hip) through the same to_f / mul_rounded / pack2_fmt of common.h, so the
-// raster equals, bit for bit, the one dta_raster_normalise makes from the host-selected, host-transposed bands.
+// The arithmetic is k_raster_normalise's (dense.hip): both take it whole from common.h's minmax_* helpers, so the raster
+// equals, bit for bit, the one dta_raster_normalise makes from the host-selected, host-transposed bands.
 #include "../../include/dta_hip.h"
 #include "kernels.h"
 
@@ -155,11 +155,8 @@ __global__ __launch_bounds__(RF_THREADS) void k_reflectance_normalise(ReflArgs a
     lo = fminf(lo, s_red[(k << a.np_log2) + p]);
     hi = fmaxf(hi, s_red[RF_THREADS + (k << a.np_log2) + p]);
   }
-  const float tiny = 10.f * 1.1920928955078125e-07f;   // scikit-learn: ranges below 10 * eps(float32) are "constant"
-  float rng = hi - lo;
-  if (rng < tiny) rng = 1.f;
-  const float s = 1.f / rng;
-  const float m = 0.f - mul_rounded(lo, s);
+  float s, m;
+  minmax_scale(lo, hi, &s, &m);
 
   // ---- write
   const size_t pixel = (size_t)(a.out_row0 + row) * a.cols + (size_t)(px0 + p);
@@ -172,28 +169,18 @@ __global__ __launch_bounds__(RF_THREADS) void k_reflectance_normalise(ReflArgs a
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int c = ch * 16 + q * 4 + e;
-          if (c < C) out[(size_t)c * a.P] = mul_rounded(to_f(*reinterpret_cast<const T*>(mine + o[e])), s) + m;
+          if (c < C) out[(size_t)c * a.P] = minmax_apply(to_f(*reinterpret_cast<const T*>(mine + o[e])), s, m);
         }
       }
     }
   } else {
     unsigned short* out = reinterpret_cast<unsigned short*>(a.out);
     for (int ch = g; ch < NC; ch += G) {
-      unsigned pk[8];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const i32x4 o = *reinterpret_cast<const i32x4*>(s_off + ch * 16 + q * 4);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int c = ch * 16 + q * 4 + 2 * h;
-          const float v0 = c < C ? mul_rounded(to_f(*reinterpret_cast<const T*>(mine + o[2 * h])), s) + m : 0.f;
-          const float v1 = c + 1 < C ? mul_rounded(to_f(*reinterpret_cast<const T*>(mine + o[2 * h + 1])), s) + m : 0.f;
-          pk[q * 2 + h] = pack2_fmt(v0, v1, FMT_BF16);
-        }
-      }
-      u32x4* dst = reinterpret_cast<u32x4*>(out + ((size_t)ch * a.P + pixel) * 16);
-      dst[0] = u32x4{pk[0], pk[1], pk[2], pk[3]};
-      dst[1] = u32x4{pk[4], pk[5], pk[6], pk[7]};
+      i32x4 o;      // the band offsets four at a time, as the min / max pass reads them: bands are asked for in ascending order
+      minmax_store_chunk(out, (size_t)a.P, pixel, ch, C, s, m, [&](int c) {
+        if ((c & 3) == 0) o = *reinterpret_cast<const i32x4*>(s_off + c);
+        return to_f(*reinterpret_cast<const T*>(mine + o[c & 3]));
+      });
     }
   }
 }

@@ -347,7 +347,8 @@ class DenseRaster:
     per-pixel min-max of preprocess.preprocess_batch.  precision="fp32" keeps float32 [C][H][W] (for the float32 gather),
     "bf16" the first conv's channel chunks [ceil(C / 16)][H * W][16] (for the tile gather; bf16-mode Hang2020)."""
 
-    def __init__(self, raster, clip=10, precision="bf16", device="cuda"):
+    def _place(self, device, precision):
+        """The constructors' first step: the device resolved to an index and the precision checked."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("deeptreeattention_amd.dense runs on a ROCm device only (no CPU fallback)")
@@ -355,6 +356,19 @@ class DenseRaster:
             dev = torch.device("cuda", torch.cuda.current_device())
         if precision not in ("bf16", "fp32"):
             raise ValueError("precision must be 'bf16' or 'fp32', got {!r}".format(precision))
+        self.precision, self.device = precision, dev
+
+    def _allocate(self, bands, Hh, Ww):
+        """The constructors' last step before their launch: the shape and `data` in this raster's form."""
+        self.bands, self.height, self.width = bands, Hh, Ww
+        self.shape = (bands, Hh, Ww)
+        if self.precision == "bf16":
+            self.data = torch.empty(((bands + 15) // 16) * Hh * Ww * 16, dtype=torch.int16, device=self.device)
+        else:
+            self.data = torch.empty(bands, Hh, Ww, dtype=torch.float32, device=self.device)
+
+    def __init__(self, raster, clip=10, precision="bf16", device="cuda"):
+        self._place(device, precision)
         a = raster.detach().cpu().numpy() if isinstance(raster, torch.Tensor) else np.asarray(raster)
         if a.ndim != 3:
             raise ValueError("the raster must be a band-first 3-d array")
@@ -362,14 +376,8 @@ class DenseRaster:
             a = a.astype(np.float32)
         L = _lib.lib()
         bands_raw, Hh, Ww = a.shape
-        self.bands, self.height, self.width = out_bands(bands_raw, clip), Hh, Ww
-        self.shape = (self.bands, Hh, Ww)
-        self.precision, self.device = precision, dev
-        raw = torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        if precision == "bf16":
-            self.data = torch.empty(((self.bands + 15) // 16) * Hh * Ww * 16, dtype=torch.int16, device=dev)
-        else:
-            self.data = torch.empty(self.bands, Hh, Ww, dtype=torch.float32, device=dev)
+        self._allocate(out_bands(bands_raw, clip), Hh, Ww)
+        raw = torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
         _lib.check(L.dta_raster_normalise(_lib.ptr(raw), bands_raw, Hh, Ww, clip, _DTYPES[a.dtype], int(precision == "bf16"),
                                           _lib.ptr(self.data), _lib.current_stream_ptr()), "dta_raster_normalise")
 
@@ -385,13 +393,9 @@ class DenseRaster:
         whole rows, one launch per strip (default: as many rows as 64 MiB of raw data hold -- a bound on memory, not a tuned
         value), or a device tensor, normalised in one launch."""
         from . import reflectance as R
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("deeptreeattention_amd.dense runs on a ROCm device only (no CPU fallback)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if precision not in ("bf16", "fp32"):
-            raise ValueError("precision must be 'bf16' or 'fp32', got {!r}".format(precision))
+        self = cls.__new__(cls)
+        self._place(device, precision)
+        dev = self.device
         resident = isinstance(cube, torch.Tensor) and cube.is_cuda
         if isinstance(cube, torch.Tensor) and not resident:
             cube = cube.detach().numpy()
@@ -409,16 +413,9 @@ class DenseRaster:
         Hh, Ww = r1 - r0, c1 - c0
         if Hh * Ww >= 2 ** 31:
             raise ValueError("a raster of {} x {} pixels is over int32".format(Hh, Ww))
-        self = cls.__new__(cls)
-        self.bands, self.height, self.width = len(sel), Hh, Ww
-        self.shape = (self.bands, Hh, Ww)
-        self.precision, self.device = precision, dev
+        self._allocate(len(sel), Hh, Ww)
         L = _lib.lib()
         index = torch.from_numpy(sel).to(dev, non_blocking=True)
-        if precision == "bf16":
-            self.data = torch.empty(((self.bands + 15) // 16) * Hh * Ww * 16, dtype=torch.int16, device=dev)
-        else:
-            self.data = torch.empty(self.bands, Hh, Ww, dtype=torch.float32, device=dev)
 
         def launch(strip, code, rows, out_row0):
             d = _lib.ReflectanceDesc(B, Ws, rows, c0, Ww, code, int(precision == "bf16"), Hh, out_row0)
@@ -475,6 +472,14 @@ class DenseRaster:
     def _boxes(self, boxes):
         return self._index(boxes, 4, "boxes must be a non-empty [N, 4] array of (row0, col0, row1, col1)")
 
+    def _batch(self, B, size, zero=False):
+        """The buffer a gather of B items writes, in this raster's form: float32 (B, bands, size, size), or for a bf16
+        raster int16 (B, elements of an item's tiles).  Either way t[:n] is the buffer of the first n items."""
+        make = torch.zeros if zero else torch.empty
+        if self.precision == "bf16":
+            return make(B, ((self.bands + 15) // 16) * size * size * 16, dtype=torch.int16, device=self.device)
+        return make(B, self.bands, size, size, dtype=torch.float32, device=self.device)
+
     def _gather(self, entry, o, extra, tiles, size, out):
         """The body of windows / crops: `entry`[_tiles](raster, bands, H, W, o, N, size, *extra, out, stream)."""
         L = _lib.lib()
@@ -484,7 +489,7 @@ class DenseRaster:
                 raise RuntimeError("tiles=True needs DenseRaster(..., precision='bf16')")
             numel = N * ((self.bands + 15) // 16) * size * size * 16
             if out is None:
-                out = torch.empty(numel, dtype=torch.int16, device=self.device)
+                out = self._batch(N, size).view(-1)
             elif out.dtype != torch.int16 or out.numel() != numel or not out.is_contiguous():
                 raise ValueError("out must be a contiguous int16 tensor of {} elements".format(numel))
             _lib.check(getattr(L, entry + "_tiles")(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N,
@@ -494,7 +499,7 @@ class DenseRaster:
             raise RuntimeError("the float32 batch needs DenseRaster(..., precision='fp32')")
         shape = (N, self.bands, size, size)
         if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            out = self._batch(N, size)
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32 tensor of shape {}".format(shape))
         _lib.check(getattr(L, entry)(_lib.ptr(self.data), self.bands, self.height, self.width, _lib.ptr(o), N, size, *extra,
@@ -644,18 +649,9 @@ def _share_conv1_multistage_refusals(predictor, rs, size):
     """What the shared first conv of the multi-stage route does not cover, after _multistage_years; raises before anything
     is allocated or launched.  Returns the present years' rasters."""
     mods = _share_conv1_multistage_models(predictor, size)
-    m0 = mods[0]
-    have = [r for r in rs if r is not None]
-    if not have:
-        raise ValueError("at least one year's raster must be present")
-    for r in have:
-        if not isinstance(r, DenseRaster):
-            raise TypeError("rasters must be DenseRaster objects")
-        if r.precision != m0.precision:
-            raise RuntimeError("share_conv1: {}-mode networks need DenseRaster(..., precision={!r}), not {!r}"
-                               .format(m0.precision, m0.precision, r.precision))
-        if r.shape != have[0].shape or r.device != have[0].device:
-            raise ValueError("all years' rasters must share one shape and device")
+    want = mods[0].precision
+    have = _check_rasters(rs, want, "share_conv1: {}-mode networks need DenseRaster(..., precision={!r}), not {!r}"
+                          .format(want, want, "fp32" if want == "bf16" else "bf16"))      # (a raster is in one of the two)
     for m in mods:
         w = next(t for t in m.parameters() if t.dim() == 4)
         if w.shape[1] != have[0].bands:
@@ -727,20 +723,26 @@ class Conv1TableYears:
         return [Conv1TableNP(t.cpu().numpy(), self.height, self.width) for t in self.data]
 
 
-def _check_years(rs):
-    """The years' rasters of a multi-stage / float32 ensemble route: fp32 DenseRasters of one shape, None = missing, at
-    least one present.  Returns the present ones.  Launches nothing."""
+def _check_rasters(rs, want, refusal, one_device=True):
+    """The raster set of a prediction route (one per year, None = missing; a single-raster route passes a list of one):
+    at least one present, DenseRasters in precision `want` -- anything else raises RuntimeError(refusal), the route's own
+    words -- of one shape and, with one_device, one device.  Returns the present ones.  Launches nothing."""
     have = [r for r in rs if r is not None]
     if not have:
         raise ValueError("at least one year's raster must be present")
     for r in have:
         if not isinstance(r, DenseRaster):
             raise TypeError("rasters must be DenseRaster objects")
-        if r.precision != "fp32":
-            raise RuntimeError("the multi-stage route reads DenseRaster(..., precision='fp32') (bf16 tiles are not taken)")
-        if r.shape != have[0].shape or r.device != have[0].device:
-            raise ValueError("all years' rasters must share one shape and device")
+        if r.precision != want:
+            raise RuntimeError(refusal)
+        if r.shape != have[0].shape or (one_device and r.device != have[0].device):
+            raise ValueError("all years' rasters must share one shape" + (" and device" if one_device else ""))
     return have
+
+
+def _check_years(rs):
+    """The years' rasters of a multi-stage / float32 ensemble route: fp32 DenseRasters."""
+    return _check_rasters(rs, "fp32", "the multi-stage route reads DenseRaster(..., precision='fp32') (bf16 tiles are not taken)")
 
 
 CrownPredictions = collections.namedtuple("CrownPredictions", "mean top_idx top_score count")
@@ -754,11 +756,8 @@ def crown_reduce(probs, crown_offsets):
     dev = probs.device
     if probs.dtype != torch.float32 or probs.dim() != 2 or not probs.is_contiguous():
         raise ValueError("probs must be a contiguous float32 [rows][classes] tensor")
-    host = crown_offsets.detach().cpu().numpy() if isinstance(crown_offsets, torch.Tensor) else np.asarray(crown_offsets)
-    host = host.astype(np.int64)
-    if host.ndim != 1 or len(host) < 2 or host[0] < 0 or (np.diff(host) < 0).any() or host[-1] > probs.shape[0]:
-        raise ValueError("crown_offsets must be non-decreasing, start at >= 0 and end within the {} rows".format(probs.shape[0]))
-    off = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+    host = _host_offsets(crown_offsets, probs.shape[0])
+    off = torch.from_numpy(host).to(dev)
     n, classes = len(host) - 1, probs.shape[1]
     out = CrownPredictions(torch.empty(n, classes, dtype=torch.float32, device=dev),
                            torch.empty(n, 2, dtype=torch.int64, device=dev),
@@ -896,17 +895,8 @@ def _predict_batches(gather, model_or_predictor, rasters, items, crown_offsets, 
             raise ValueError("a {}-year ensemble needs {} rasters (None for a missing year)".format(len(pred.nets_mod), len(pred.nets_mod)))
     else:
         rs = [rasters]
-    have = [r for r in rs if r is not None]
-    if not have:
-        raise ValueError("at least one year's raster must be present")
-    r0 = have[0]
-    for r in have:
-        if not isinstance(r, DenseRaster):
-            raise TypeError("rasters must be DenseRaster objects")
-        if r.precision != want:
-            raise RuntimeError("this network reads a DenseRaster(..., precision={!r}) (dense.raster_precision)".format(want))
-        if r.shape != r0.shape:
-            raise ValueError("all years' rasters must share one shape")
+    r0 = _check_rasters(rs, want, "this network reads a DenseRaster(..., precision={!r}) (dense.raster_precision)".format(want),
+                        one_device=False)[0]
     dev = r0.device
     o = gather.index(r0, items)
     L = _lib.lib()
@@ -919,15 +909,9 @@ def _predict_batches(gather, model_or_predictor, rasters, items, crown_offsets, 
     tiles = want == "bf16"
     if share_conv1:
         table = r0.conv1_table(pred, size=size)
-    elif tiles:
-        per = ((r0.bands + 15) // 16) * size * size * 16
-        bufs = [torch.empty(B * per, dtype=torch.int16, device=dev)]
     else:
-        per = r0.bands * size * size
-        bufs = [torch.empty(B, r0.bands, size, size, dtype=torch.float32, device=dev) if r is not None else None for r in rs]
-        if any(b is None for b in bufs):
-            zeros = torch.zeros(B, r0.bands, size, size, dtype=torch.float32, device=dev)
-            bufs = [zeros if b is None else b for b in bufs]
+        zeros = r0._batch(B, size, zero=True) if any(r is None for r in rs) else None      # ONE stands in for every missing year
+        bufs = [zeros if r is None else r0._batch(B, size) for r in rs]
     st = _lib.current_stream_ptr()
     for n0 in range(0, N, B):
         n = min(B, N - n0)
@@ -936,12 +920,8 @@ def _predict_batches(gather, model_or_predictor, rasters, items, crown_offsets, 
             table.gather(ob, pred.conv1_slot(n, r0.bands))
             logits = pred.logits_from_conv1()
         else:
-            if tiles:
-                x = gather.one(r0, ob, tiles=True, size=size, out=bufs[0][:n * per])
-            else:
-                xs = [b[:n] if r is None else gather.one(r, ob, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
-                x = xs if pred.ensemble else xs[0]
-            logits = pred.logits_of(x)
+            xs = [b[:n] if r is None else gather.one(r, ob, tiles=tiles, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
+            logits = pred.logits_of(xs if pred.ensemble else xs[0])
         _lib.check(L.dta_softmax_top2(_lib.ptr(logits), n, classes, _lib.ptr(probs[n0:n0 + n]) if keep else None,
                                       _lib.ptr(top_idx[n0:n0 + n]), _lib.ptr(top_score[n0:n0 + n]), st), "dta_softmax_top2")
     crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
@@ -1051,10 +1031,8 @@ def _predict_batches_multistage(gather, predictor, rasters, items, crown_offsets
     if share_conv1:
         table = Conv1TableYears(rs, predictor)
     else:
-        zeros = None
-        if len(have) < Y:      # ONE persistent zero batch stands in for every missing year
-            zeros = torch.zeros(B, r0.bands, size, size, dtype=torch.float32, device=dev)
-        bufs = [zeros if r is None else torch.empty(B, r0.bands, size, size, dtype=torch.float32, device=dev) for r in rs]
+        zeros = r0._batch(B, size, zero=True) if len(have) < Y else None      # ONE persistent zero batch stands in for every missing year
+        bufs = [zeros if r is None else r0._batch(B, size) for r in rs]
     banks = [torch.zeros(Y, dtype=torch.float32, device=dev) for _ in range(2)]
     bank = 0
     for n0 in range(0, N, B):
@@ -1151,17 +1129,11 @@ def _predict_batches_metadata(gather, predictor, raster, site, items, crown_offs
     top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
     top_score = torch.empty(N, 2, dtype=torch.float32, device=dev)
     probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
-    tiles = want == "bf16"
-    if tiles:
-        per = ((raster.bands + 15) // 16) * size * size * 16
-        buf = torch.empty(B * per, dtype=torch.int16, device=dev)
-    else:
-        buf = torch.empty(B, raster.bands, size, size, dtype=torch.float32, device=dev)
+    buf = raster._batch(B, size)
     ws = predictor.table()
     for n0 in range(0, N, B):
         n = min(B, N - n0)
-        ob = o[n0:n0 + n]
-        x = gather.one(raster, ob, tiles=True, size=size, out=buf[:n * per]) if tiles else gather.one(raster, ob, size=size, out=buf[:n])
+        x = gather.one(raster, o[n0:n0 + n], tiles=want == "bf16", size=size, out=buf[:n])
         scores = sens.logits_of(x)
         predictor.head(scores, n, ws, site, None, probs[n0:n0 + n] if keep else None, top_idx[n0:n0 + n], top_score[n0:n0 + n])
     crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
