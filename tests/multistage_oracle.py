@@ -33,9 +33,11 @@ CASES = {
 TAU = 2e-6
 
 
-def _near_decisions(year_cache):
+def _near_decisions(year_cache, attention=False):
     """The ReLU / max-pool decisions of one network's forward that float32 rounding can take the other way:
-    [(layer, "relu", index)] and [(layer, "pool", window index, runner-up slot)]."""
+    [(layer, "relu", index)] and [(layer, "pool", window index, runner-up slot)]; attention=True: also the ReLUs inside the
+    attention blocks, [(layer, "att:<cache key>", index)] (spectral: h0; spatial: m0, t1p -- sums of 32..128 products of
+    unit-scale factors, the same rounding scale)."""
     out = []
     for L, (cc, _, _) in enumerate(year_cache["layers"]):
         v = cc["v"]
@@ -50,6 +52,11 @@ def _near_decisions(year_cache):
             second = np.take_along_axis(xc, order[..., 2:3], -1)[..., 0]
             for idx in zip(*np.nonzero((top - second < TAU) & (second > 0))):
                 out.append((L, "pool", idx, int(order[idx][2])))
+    if attention:
+        for L, (_, ac, _) in enumerate(year_cache["layers"]):
+            for key in ("h0", "m0", "t1p"):
+                if key in ac:
+                    out += [(L, "att:" + key, idx) for idx in zip(*np.nonzero(np.abs(ac[key]) < TAU))]
     return out
 
 
@@ -57,10 +64,11 @@ def _toggled(year_cache, dec):
     """Context: the cache with one decision taken the other way (restored on exit)."""
     @contextlib.contextmanager
     def ctx():
-        cc = year_cache["layers"][dec[0]][0]
-        key, idx = ("v", dec[2]) if dec[1] == "relu" else ("arg", dec[2])
+        att = dec[1].startswith("att:")      # (the backward reads only the sign of a ReLU input)
+        cc = year_cache["layers"][dec[0]][1 if att else 0]
+        key, idx = (dec[1][4:], dec[2]) if att else ("v", dec[2]) if dec[1] == "relu" else ("arg", dec[2])
         old = cc[key][idx]
-        cc[key][idx] = (-1.0 if old > 0 else 1.0) if dec[1] == "relu" else dec[3]
+        cc[key][idx] = dec[3] if dec[1] == "pool" else (-1.0 if old > 0 else 1.0)
         try:
             yield
         finally:
