@@ -19,6 +19,9 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.reflectance  <->  src/Hyperspectral.py:138-219 generate_raster / calc_clip_index: the band mask, the
                                      clip window and the band-first transpose between a pixel-interleaved reflectance cube
                                      and the resident raster (DenseRaster.from_reflectance: one launch per strip of rows)
+    deeptreeattention_amd.boundary   <->  gpd.clip(crowns, boundary) in abundance.py, create_prediction_shp.py and
+                                     src/multinomial.py: which crown boxes, points and raster cells lie inside the site's
+                                     boundary polygon, from a resident edge table (one launch each)
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

@@ -97,6 +97,8 @@ ELEM_F32, ELEM_BF16, ELEM_F16 = 0, 1, 2   # DTA_ELEM_*
 RGB_CROPS_MAX_GROUPS = 1024   # DTA_RGB_CROPS_MAX_GROUPS
 RGB_CROPS_MAX_SIZE = 512   # DTA_RGB_CROPS_MAX_SIZE
 REFLECTANCE_MAX_BANDS = 1024   # DTA_REFLECTANCE_MAX_BANDS
+BOUNDARY_EDGE_CHUNK = 1024   # DTA_BOUNDARY_EDGE_CHUNK
+BOUNDARY_MAX_EDGES = 1 << 20   # DTA_BOUNDARY_MAX_EDGES
 
 
 class ReflectanceDesc(C.Structure):     # dta_reflectance_desc
@@ -364,6 +366,14 @@ def lib():
         # reflectance cube -> resident raster: band selection, window, min-max and transpose in one pass (reflectance.hip)
         L.dta_reflectance_normalise.restype = C.c_int
         L.dta_reflectance_normalise.argtypes = [C.POINTER(ReflectanceDesc), vp, vp, C.c_int, vp, vp]
+        # site boundary clip: points, crown boxes and raster cells inside a polygon (boundary.hip); org and transform are
+        # HOST arrays
+        L.dta_boundary_points.restype = C.c_int
+        L.dta_boundary_points.argtypes = [vp, C.c_int, c_double_p, vp, C.c_longlong, vp, vp]
+        L.dta_boundary_boxes.restype = C.c_int
+        L.dta_boundary_boxes.argtypes = [vp, C.c_int, c_double_p, vp, vp, c_double_p, C.c_longlong, vp, vp]
+        L.dta_boundary_raster.restype = C.c_int
+        L.dta_boundary_raster.argtypes = [vp, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

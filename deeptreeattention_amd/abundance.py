@@ -125,7 +125,8 @@ def _bins(label, S, mask):
 
 def counts_np(label, S, mask=None):
     """Trees per species: int64 [S + 1], bin S for every label outside [0, S) (DEAD, the walk's unresolved -1); a crown
-    with mask == 0 is counted nowhere (the reference's clip to a boundary, decided by the caller)."""
+    with mask == 0 is counted nowhere (the reference's clip to a boundary, decided by the caller: boundary.Boundary.clip
+    gives that mask on the device)."""
     bins, _, live = _bins(label, int(S), mask)
     return np.bincount(bins[live], minlength=int(S) + 1).astype(np.int64)
 

@@ -10,7 +10,8 @@ from a resident raster and applies the keep rule; the result is the `mask` abund
 it indexes the boxes dense.predict_crops* take.
 
 A crown is a pixel box (row0, col0, row1, col1), half-open, as everywhere in dense.py; it is clipped to the raster.
-Georeferencing and polygon rasterisation (which cells a polygon owns) stay with the caller, as in dense.py.
+Georeferencing and polygon rasterisation (which cells a polygon owns) stay with the caller, as in dense.py (for the site's
+boundary polygon: boundary.Boundary.clip on pixel boxes with the raster's transform, and Boundary.rasterise).
 
 For one crown, with every operation rounded to float32 on its own (np.nanpercentile's arithmetic on float32 input; a fused
 multiply-add, a float64 lerp or a float64 `t` do NOT give the reference's bits):

@@ -930,6 +930,36 @@ typedef struct dta_reflectance_desc {
 int dta_reflectance_normalise(const dta_reflectance_desc* d, const void* strip, const int* band_index, int bands, void* out,
                               void* stream);
 
+/* ---- Site boundary clip: which points, crown boxes and raster cells lie inside a polygon (the reference's
+ * gpd.clip(crowns, boundary) in abundance.py:24-35, create_prediction_shp.py:33-41 and src/multinomial.py:16-19).
+ * edges: double [n_edges][4] (ax, ay, bx, by) on the device, every ring of the (Multi)Polygon closed, any orientation, `org`
+ * already subtracted; the region is the even-odd interior of all rings together.  org: double [2] on the HOST, subtracted
+ * from every query coordinate first.  All arithmetic in double, every product and every difference rounded on its own (no
+ * FMA, no division); deeptreeattention_amd/boundary.py: contains_np / boxes_np / rasterise_np are the definition and the
+ * kernels equal them bit for bit.
+ *   point p, edge k:  straddle = (ay > py) != (by > py);  dx = bx - ax;  dy = by - ay;  l = (px - ax) * dy;
+ *                     r = (py - ay) * dx;  left = dy > 0 ? l < r : l > r;  inside = parity of (straddle & left) over the
+ *                     edges; a NaN coordinate gives 0
+ *   box (x0, y0, x1, y1):  code 0 if a coordinate is not finite or x1 < x0 or y1 < y0.  Edge k touches the filled rectangle
+ *                     unless both of its ends are on the outer side of one box side (ax < x0 && bx < x0, ...) or the four
+ *                     corner signs s(c) = dx * (cy - ay) - dy * (cx - ax) are all > 0 or all < 0.  code = 1 if any edge
+ *                     touches, else 2 if (x0, y0) is inside, else 0
+ *   pixel box (row0, col0, row1, col1) with transform (x0, a, y0, e) (double [4] on the HOST; rasterio's
+ *                     Affine(a, 0, x0, 0, e, y0)):  x = x0 + col * a, y = y0 + row * e, then min / max per axis
+ *   raster cell (r, c):  the point (x0 + (c + .5) * a, y0 + (r + .5) * e)
+ * out: bytes, every element overwritten (points, raster: 0 / 1; boxes: the code).  One launch each, no workspace, no
+ * atomics on global memory.  Refused on the host, before any launch: a null edges / org / queries / out; n < 1 or
+ * n >= 2^31; n_edges outside 3 .. 2^20; height or width < 1, height * width over int32; both or neither of geo_boxes and
+ * pixel_boxes; pixel_boxes without transform, geo_boxes with one; a non-finite org or transform; a == 0 or e == 0. */
+#define DTA_BOUNDARY_EDGE_CHUNK 1024        /* edges staged through LDS at a time */
+#define DTA_BOUNDARY_MAX_EDGES (1 << 20)
+int dta_boundary_points(const double* edges, int n_edges, const double* org, const double* points, long long n,
+                        unsigned char* out, void* stream);
+int dta_boundary_boxes(const double* edges, int n_edges, const double* org, const double* geo_boxes, const int* pixel_boxes,
+                       const double* transform, long long n, unsigned char* out, void* stream);
+int dta_boundary_raster(const double* edges, int n_edges, const double* org, int height, int width, const double* transform,
+                        unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
