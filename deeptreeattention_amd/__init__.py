@@ -22,6 +22,8 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.boundary   <->  gpd.clip(crowns, boundary) in abundance.py, create_prediction_shp.py and
                                      src/multinomial.py: which crown boxes, points and raster cells lie inside the site's
                                      boundary polygon, from a resident edge table (one launch each)
+    deeptreeattention_amd.split      <->  src/data.py sample_plots + train_test_split: the search for the plot-level
+                                     train/test split with the most test species, every iteration in one launch
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

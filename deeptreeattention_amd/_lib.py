@@ -99,6 +99,8 @@ RGB_CROPS_MAX_SIZE = 512   # DTA_RGB_CROPS_MAX_SIZE
 REFLECTANCE_MAX_BANDS = 1024   # DTA_REFLECTANCE_MAX_BANDS
 BOUNDARY_EDGE_CHUNK = 1024   # DTA_BOUNDARY_EDGE_CHUNK
 BOUNDARY_MAX_EDGES = 1 << 20   # DTA_BOUNDARY_MAX_EDGES
+SPLIT_MAX_SPECIES = 256   # DTA_SPLIT_MAX_SPECIES
+SPLIT_MAX_CANDIDATES = 4096   # DTA_SPLIT_MAX_CANDIDATES
 
 
 class ReflectanceDesc(C.Structure):     # dta_reflectance_desc
@@ -374,6 +376,10 @@ def lib():
         L.dta_boundary_boxes.argtypes = [vp, C.c_int, c_double_p, vp, vp, c_double_p, C.c_longlong, vp, vp]
         L.dta_boundary_raster.restype = C.c_int
         L.dta_boundary_raster.argtypes = [vp, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, vp, vp]
+        # train/test plot split search: every iteration in one launch (split.hip); floor is a HOST array
+        L.dta_split_search.restype = C.c_int
+        L.dta_split_search.argtypes = [vp, vp, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
+                                       C.c_ulonglong, vp, vp, vp, vp, vp, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

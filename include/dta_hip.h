@@ -960,6 +960,40 @@ int dta_boundary_boxes(const double* edges, int n_edges, const double* org, cons
 int dta_boundary_raster(const double* edges, int n_edges, const double* org, int height, int width, const double* transform,
                         unsigned char* out, void* stream);
 
+/* ---- Train/test plot split search: the reference's train_test_split (src/data.py:165-236), which runs sample_plots
+ * (:108-162) config["iterations"] times on a dask cluster and keeps the split with the most test species.  Everything
+ * depends on integer tables over plots x species (deeptreeattention_amd/split.py builds them; search_np there is the
+ * definition, and the kernels equal it bit for bit):
+ *   A individuals, B individuals with at least one row that is not "fixed", R rows (individual x year)
+ *   rows:   int [candidates][3][SP] on the device: A, B, R of each candidate plot, SP = species rounded up to a multiple of 4,
+ *           the padding zero
+ *   totals: int [2][SP] on the device: totA and totR, the sums of A and R over ALL plots
+ *   floor:  double [species] on the HOST: max((double)totA[s] * 0.05, (double)min_test)
+ * Iteration t (t = 0 .. iterations - 1) orders the candidates ascending by (draw32, j) with
+ *   draw32 = mix(((first_iteration + t) * candidates + j) * 0x9E3779B97F4A7C15 + mix(seed * 0x9E3779B97F4A7C15 + 1)) >> 32
+ * (all modulo 2^64; mix as for dta_abundance_resample), or, where `orders` (int [iterations][candidates] on the device) is
+ * given, by row t of it, which the CALLER has checked to be a permutation (an entry outside 0 .. candidates - 1 is only
+ * kept from leaving the table).  Then
+ *   cnt = 0; wanted[s] = 1; inc[p] = 0
+ *   for p in that order:  if any s has A[p][s] > 0 and wanted[s]:  inc[p] = 1; cnt += A[p]; wanted[s] = !((double)cnt[s] > floor[s])
+ *   T[s] = (sum of B over inc)[s] >= min_test  &&  totA[s] - cnt[s] >= min_train
+ *   species[t] = popcount(T);  train_rows[t] = sum over T of (totR[s] - (sum of R over inc)[s]);  test_plots[t] = popcount(inc)
+ *   membership[t][p] = inc[p] and taxa[t][s] = T[s], bytes, where those pointers are not null
+ *   best = { t, species[t], train_rows[t], test_plots[t] } of the lexicographic maximum of (species, train_rows), the
+ *          smallest t on a full tie
+ * Two launches (one wavefront per iteration; one workgroup for the best), no workspace, no atomics; every output element
+ * is overwritten.  Refused on the host, before any launch: a null rows / totals / floor / species / train_rows /
+ * test_plots / best; species outside 1 .. DTA_SPLIT_MAX_SPECIES; candidates outside 1 .. DTA_SPLIT_MAX_CANDIDATES (the
+ * sort keeps 8 bytes per candidate, rounded up to a power of two, in LDS: 32 KB per wavefront at 4096, five wavefronts per
+ * compute unit; twice that would be the 64 KB a workgroup gets by default and leave two); iterations < 0 (0 launches
+ * nothing and writes nothing); min_train or min_test below 1; rows or totals not 16-byte aligned; a floor that is not finite. */
+#define DTA_SPLIT_MAX_SPECIES 256
+#define DTA_SPLIT_MAX_CANDIDATES 4096
+int dta_split_search(const int* rows, const int* totals, int candidates, int species, const double* floor, int min_train,
+                     int min_test, int iterations, unsigned long long seed, unsigned long long first_iteration,
+                     const int* orders, int* out_species, long long* out_train_rows, int* out_test_plots, long long* best,
+                     unsigned char* membership, unsigned char* taxa, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
