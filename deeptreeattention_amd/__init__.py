@@ -24,6 +24,9 @@ The package mirrors the reference's module names for this path only:
                                      boundary polygon, from a resident edge table (one launch each)
     deeptreeattention_amd.split      <->  src/data.py sample_plots + train_test_split: the search for the plot-level
                                      train/test split with the most test species, every iteration in one launch
+    deeptreeattention_amd.stems      <->  src/generate.py process_plot + create_boxes + choose_box: which crown box a
+                                     field-measured stem gets (join, fallback box, nearest centre) and which stem a box
+                                     keeps (the tallest), all plots of a site in one chain of three launches
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

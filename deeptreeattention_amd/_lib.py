@@ -101,6 +101,7 @@ BOUNDARY_EDGE_CHUNK = 1024   # DTA_BOUNDARY_EDGE_CHUNK
 BOUNDARY_MAX_EDGES = 1 << 20   # DTA_BOUNDARY_MAX_EDGES
 SPLIT_MAX_SPECIES = 256   # DTA_SPLIT_MAX_SPECIES
 SPLIT_MAX_CANDIDATES = 4096   # DTA_SPLIT_MAX_CANDIDATES
+STEMS_CHUNK = 1024   # DTA_STEMS_CHUNK
 
 
 class ReflectanceDesc(C.Structure):     # dta_reflectance_desc
@@ -380,6 +381,10 @@ def lib():
         L.dta_split_search.restype = C.c_int
         L.dta_split_search.argtypes = [vp, vp, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                        C.c_ulonglong, vp, vp, vp, vp, vp, vp, vp, vp]
+        # field stems to crown boxes: join, nearest box, one stem per box (stems.hip); tables sorted by plot
+        L.dta_stems_assign.restype = C.c_int
+        L.dta_stems_assign.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_longlong, C.c_int, C.c_double, vp, vp, vp,
+                                       vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -1,0 +1,296 @@
+// Field stems to crown boxes (reference src/generate.py: process_plot :92-153, create_boxes :73-90, choose_box :62-71 and
+// points_to_crowns :239: gpd.sjoin per plot and two Python groupby loops on the host).  deeptreeattention_amd/stems.py holds
+// the definition (assign_np); these kernels equal it bit for bit: float64 throughout, every product, sum and difference
+// rounded on its own, and every reduction is "the smallest, the lowest index among equals", which does not depend on how
+// the tables are cut into chunks.  One stem per lane in each of the three launches:
+//   k_stems_choose    the closed point-in-box join over the predicted boxes of the stem's plot and the nearest candidate;
+//                     writes choice (-1: none) and a provisional status (4 no box possible, 2 missing, 1 has a box)
+//   k_stems_fallback  for the missing stems: the same over the fallback boxes of the missing stems of the plot; reads
+//                     status, writes choice (nobody reads choice here, nobody writes status)
+//   k_stems_resolve   one stem per box, from the stem's side: one pass over the stems of the plot that chose the same box
+//                     finds the group's size, hmax, the tied set's size, cmax on it and the lowest index; writes status and
+//                     crowns
+// Both tables are sorted by plot, so what the 256 stems of a workgroup can meet is one contiguous range of rows: it is
+// staged through LDS in chunks of ST_CHUNK rows and every lane walks the rows of its own plot's segment only.  The range is
+// the smallest start and the largest end over the workgroup's lanes, so an unsorted table costs time and nothing else.
+// Every box_start / point_start entry is clamped into its table and a plot code outside 0 .. plots-1 gives status 4:
+// nothing reads outside a table whatever the arrays hold.  No atomics, no workspace but choice, no private segment (the
+// walk's four rows in flight are registers).
+#include "../../include/dta_hip.h"
+#include "common.h"
+
+#include <climits>
+#include <cmath>
+
+// no fused multiply-add in this file: (cx - px) * (cx - px) + (cy - py) * (cy - py) is the definition's operations one by
+// one (hipcc contracts by default; see mul_rounded)
+#pragma clang fp contract(off)
+
+namespace dta {
+
+constexpr int ST_THREADS = 256;
+constexpr int ST_WAVES = ST_THREADS / 64;
+constexpr int ST_CHUNK = DTA_STEMS_CHUNK;
+
+// x * y rounded to float64 on its own: the empty asm makes the product opaque, so no later addition is fused into it
+__device__ __forceinline__ double mul_rounded(double x, double y) {
+  double p = x * y;
+  asm("" : "+v"(p));
+  return p;
+}
+
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN, +-inf
+
+__device__ __forceinline__ int clamp_row(int v, int rows) { return v < 0 ? 0 : (v > rows ? rows : v); }
+
+// The rows [lo, hi) of plot p in a table of `rows` rows, clamped into it; p is inside 0 .. plots-1 (start has plots + 1
+// entries).
+__device__ __forceinline__ void plot_segment(const int* start, int p, int rows, int& lo, int& hi) {
+  lo = clamp_row(start[p], rows);
+  hi = clamp_row(start[p + 1], rows);
+  hi = hi < lo ? lo : hi;
+}
+
+// The smallest lo and the largest hi over the workgroup, the same in every thread.  red: 2 * ST_WAVES ints of LDS.
+__device__ __forceinline__ void workgroup_range(int& lo, int& hi, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
+    lo = a < lo ? a : lo;
+    hi = b > hi ? b : hi;
+  }
+  if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = lo; red[2 * (threadIdx.x >> 6) + 1] = hi; }
+  __syncthreads();
+  lo = red[0]; hi = red[1];
+#pragma unroll
+  for (int w = 1; w < ST_WAVES; ++w) {
+    lo = red[2 * w] < lo ? red[2 * w] : lo;
+    hi = red[2 * w + 1] > hi ? red[2 * w + 1] : hi;
+  }
+}
+
+// Box (x0, y0, x1, y1) against the stem (px, py): steps 1 and 3.  Taken iff it is a candidate and nearer than the best so
+// far; rows come in ascending order, so among equals the lowest index stays.  Selects, no branch: the walk below unrolls.
+__device__ __forceinline__ void consider(double x0, double y0, double x1, double y1, double px, double py, int j, int& best,
+                                         double& bestd) {
+  const bool cand = (x0 <= px) & (px <= x1) & (y0 <= py) & (py <= y1);
+  const double cx = (x0 + x1) * 0.5, cy = (y0 + y1) * 0.5;
+  const double dx = cx - px, dy = cy - py;
+  double d2 = mul_rounded(dx, dx) + mul_rounded(dy, dy);
+  d2 = d2 == d2 ? d2 : INFINITY;
+  const bool take = cand & ((best < 0) | (d2 < bestd));
+  best = take ? j : best;
+  bestd = take ? d2 : bestd;
+}
+
+// The rows [a, b) of the table, staged from row `base` on, against the stem (px, py), four at a time: the four rows' LDS
+// reads are issued before the first is used (one wave per SIMD has nothing else to hide their latency behind).
+// box(k, x0, y0, x1, y1): staged row k as a box.
+template <class Box>
+__device__ __forceinline__ void walk(int a, int b, int base, double px, double py, int& best, double& bestd, Box box) {
+  int j = a;
+  for (; j <= b - 4; j += 4) {                             // (not j + 4 <= b: a lane without rows has a = INT_MAX, b = 0)
+    double x0[4], y0[4], x1[4], y1[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) box(j - base + u, x0[u], y0[u], x1[u], y1[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) consider(x0[u], y0[u], x1[u], y1[u], px, py, j + u, best, bestd);
+  }
+  for (; j < b; ++j) {
+    double x0, y0, x1, y1;
+    box(j - base, x0, y0, x1, y1);
+    consider(x0, y0, x1, y1, px, py, j, best, bestd);
+  }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stems_choose(const double* boxes, const int* box_start, int M,
+                                                             const double* points, const int* point_plot, int N, int plots,
+                                                             long long* choice, unsigned char* status) {
+  __shared__ double sh[4 * ST_CHUNK];
+  __shared__ int red[2 * ST_WAVES];
+  const long long i = (long long)blockIdx.x * ST_THREADS + threadIdx.x;
+  const bool have = i < N;
+  double px = 0.0, py = 0.0;
+  int lo = INT_MAX, hi = 0;                                // of this lane: no rows
+  bool live = false;
+  if (have) {
+    const int p = point_plot[i];
+    px = points[2 * i]; py = points[2 * i + 1];
+    live = p >= 0 && p < plots && finite_d(px) && finite_d(py);
+    if (live) plot_segment(box_start, p, M, lo, hi);
+  }
+  int wlo = lo, whi = hi;
+  workgroup_range(wlo, whi, red);
+  int best = -1;
+  double bestd = 0.0;
+  for (int base = wlo; base < whi;) {                      // the same trips, the same barriers in every thread
+    const int cnt = whi - base < ST_CHUNK ? whi - base : ST_CHUNK;
+    __syncthreads();                                       // the previous chunk has been read by every lane
+    const double* src = boxes + 4 * (size_t)base;
+    if (cnt == ST_CHUNK) {                                 // a whole chunk: every load in flight before the first store
+#pragma unroll
+      for (int u = 0; u < 4 * ST_CHUNK / ST_THREADS; ++u) sh[u * ST_THREADS + threadIdx.x] = src[u * ST_THREADS + threadIdx.x];
+    } else {
+      for (int k = threadIdx.x; k < 4 * cnt; k += ST_THREADS) sh[k] = src[k];
+    }
+    __syncthreads();
+    const int a = lo > base ? lo : base, b = hi < base + cnt ? hi : base + cnt;
+    walk(a, b, base, px, py, best, bestd, [&](int k, double& x0, double& y0, double& x1, double& y1) {
+      x0 = sh[4 * k]; y0 = sh[4 * k + 1]; x1 = sh[4 * k + 2]; y1 = sh[4 * k + 3];
+    });
+    base += cnt;
+  }
+  if (have) {
+    choice[i] = best;
+    status[i] = !live ? 4 : (best >= 0 ? 1 : 2);
+  }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stems_fallback(const double* points, const int* point_plot,
+                                                               const int* point_start, int N, int plots, double size, int M,
+                                                               const unsigned char* status, long long* choice) {
+  __shared__ double sh[2 * ST_CHUNK];                      // (x, y) of a staged stem, x = NaN if it is not missing
+  __shared__ int red[2 * ST_WAVES];
+  const long long i = (long long)blockIdx.x * ST_THREADS + threadIdx.x;
+  const bool have = i < N;
+  double px = 0.0, py = 0.0;
+  int lo = INT_MAX, hi = 0;
+  bool live = false;
+  if (have && status[i] == 2) {
+    const int p = point_plot[i];
+    px = points[2 * i]; py = points[2 * i + 1];
+    live = p >= 0 && p < plots;
+    if (live) plot_segment(point_start, p, N, lo, hi);
+  }
+  int wlo = lo, whi = hi;
+  workgroup_range(wlo, whi, red);
+  int best = -1;
+  double bestd = 0.0;
+  for (int base = wlo; base < whi;) {
+    const int cnt = whi - base < ST_CHUNK ? whi - base : ST_CHUNK;
+    __syncthreads();
+    for (int k = threadIdx.x; k < cnt; k += ST_THREADS) {
+      const size_t g = (size_t)base + k;
+      sh[2 * k] = status[g] == 2 ? points[2 * g] : NAN;
+      sh[2 * k + 1] = points[2 * g + 1];
+    }
+    __syncthreads();
+    const int a = lo > base ? lo : base, b = hi < base + cnt ? hi : base + cnt;
+    walk(a, b, base, px, py, best, bestd, [&](int k, double& x0, double& y0, double& x1, double& y1) {
+      const double qx = sh[2 * k], qy = sh[2 * k + 1];
+      x0 = qx - size; y0 = qy - size; x1 = qx + size; y1 = qy + size;
+    });
+    base += cnt;
+  }
+  if (live) choice[i] = (long long)M + (best >= 0 ? (long long)best : i);     // (a stem lies in its own box: best < 0 needs a broken table)
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stems_resolve(const double* boxes, int M, const double* points,
+                                                              const int* point_plot, const int* point_start,
+                                                              const double* height, const double* chm, int N, int plots,
+                                                              double size, const long long* choice, unsigned char* status,
+                                                              double* crowns) {
+  __shared__ long long shc[ST_CHUNK];
+  __shared__ double shh[ST_CHUNK];
+  __shared__ double shm[ST_CHUNK];
+  __shared__ int red[2 * ST_WAVES];
+  const long long i = (long long)blockIdx.x * ST_THREADS + threadIdx.x;
+  const bool have = i < N;
+  long long mine = -1;
+  int lo = INT_MAX, hi = 0;
+  bool live = false;
+  if (have) {
+    const int p = point_plot[i];
+    mine = choice[i];
+    live = mine >= 0 && p >= 0 && p < plots;
+    if (live) plot_segment(point_start, p, N, lo, hi);
+  }
+  int wlo = lo, whi = hi;
+  workgroup_range(wlo, whi, red);
+  // G: the stems of the plot with the same choice; S: those of G at hmax; then those of S at cmax
+  int n = 0, nS = 0;
+  bool hasH = false, hasC = false;
+  double hmax = 0.0, cmax = 0.0;
+  long long lowS = -1, lowC = -1;
+  for (int base = wlo; base < whi;) {
+    const int cnt = whi - base < ST_CHUNK ? whi - base : ST_CHUNK;
+    __syncthreads();
+    for (int k = threadIdx.x; k < cnt; k += ST_THREADS) {
+      const size_t g = (size_t)base + k;
+      shc[k] = choice[g];
+      shh[k] = height[g];
+      shm[k] = chm ? chm[g] : NAN;
+    }
+    __syncthreads();
+    const int a = lo > base ? lo : base, b = hi < base + cnt ? hi : base + cnt;
+    for (int j = a; j < b; ++j) {
+      if (shc[j - base] != mine) continue;
+      const double h = shh[j - base], c = shm[j - base];
+      ++n;
+      if (h == h) {
+        if (!hasH || h > hmax) {
+          hasH = true; hmax = h; nS = 1; lowS = j;
+          hasC = c == c; cmax = c; lowC = j;
+        } else if (h == hmax) {
+          ++nS;
+          if (c == c && (!hasC || c > cmax)) { hasC = true; cmax = c; lowC = j; }
+        }
+      }
+    }
+    base += cnt;
+  }
+  if (!have) return;
+  double x0 = NAN, y0 = NAN, x1 = NAN, y1 = NAN;
+  unsigned char st = 4;
+  if (live) {
+    const unsigned char kept = mine < M ? 1 : 2;
+    if (mine < M) {
+      const double* e = boxes + 4 * (size_t)mine;
+      x0 = e[0]; y0 = e[1]; x1 = e[2]; y1 = e[3];
+    } else {
+      const size_t k = (size_t)(mine - M);                 // < N: k_stems_fallback wrote M + a row of the table
+      const double qx = points[2 * k], qy = points[2 * k + 1];
+      x0 = qx - size; y0 = qy - size; x1 = qx + size; y1 = qy + size;
+    }
+    if (n <= 1) st = kept;
+    else if (nS == 0) st = 3;
+    else if (nS == 1 || !chm) st = lowS == i ? kept : 0;
+    else if (!hasC) st = 3;
+    else st = lowC == i ? kept : 0;
+  }
+  status[i] = st;
+  double* out = crowns + 4 * (size_t)i;
+  out[0] = x0; out[1] = y0; out[2] = x1; out[3] = y1;
+}
+
+}  // namespace dta
+
+using namespace dta;
+
+extern "C" int dta_stems_assign(const double* boxes, const int* box_start, long long n_boxes, const double* points,
+                                const int* point_plot, const int* point_start, const double* height, const double* chm,
+                                long long n_points, int plots, double size, long long* choice_out, unsigned char* status_out,
+                                double* crowns_out, void* stream) {
+  const char* who = "dta_stems_assign";
+  if (!boxes || !box_start || !points || !point_plot || !point_start || !height || !choice_out || !status_out || !crowns_out) {
+    dta_set_error("%s: null argument", who);
+    return 1;
+  }
+  if (n_points < 1 || n_points > 0x7FFFFFFFll) { dta_set_error("%s: bad shape: n_points=%lld (1 .. 2^31 - 1)", who, n_points); return 1; }
+  if (n_boxes < 0 || n_boxes > 0x7FFFFFFFll) { dta_set_error("%s: bad shape: n_boxes=%lld (0 .. 2^31 - 1)", who, n_boxes); return 1; }
+  if (plots < 1) { dta_set_error("%s: plots=%d is below 1", who, plots); return 1; }
+  if (!std::isfinite(size) || !(size > 0.0)) { dta_set_error("%s: size=%g is not a finite number above 0", who, size); return 1; }
+  const int N = (int)n_points, M = (int)n_boxes;
+  const unsigned grid = (unsigned)((n_points + ST_THREADS - 1) / ST_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_stems_choose, dim3(grid), dim3(ST_THREADS), 0, s, boxes, box_start, M, points, point_plot, N, plots,
+                     choice_out, status_out);
+  DTA_CHECK_LAUNCH("k_stems_choose");
+  hipLaunchKernelGGL(k_stems_fallback, dim3(grid), dim3(ST_THREADS), 0, s, points, point_plot, point_start, N, plots, size, M,
+                     status_out, choice_out);
+  DTA_CHECK_LAUNCH("k_stems_fallback");
+  hipLaunchKernelGGL(k_stems_resolve, dim3(grid), dim3(ST_THREADS), 0, s, boxes, M, points, point_plot, point_start, height, chm,
+                     N, plots, size, choice_out, status_out, crowns_out);
+  DTA_CHECK_LAUNCH("k_stems_resolve");
+  return 0;
+}

@@ -994,6 +994,38 @@ int dta_split_search(const int* rows, const int* totals, int candidates, int spe
                      const int* orders, int* out_species, long long* out_train_rows, int* out_test_plots, long long* best,
                      unsigned char* membership, unsigned char* taxa, void* stream);
 
+/* ---- Field stems to crown boxes: which predicted crown box a field-measured stem gets and which stem a box keeps (the
+ * reference's process_plot with create_boxes and choose_box, src/generate.py:62-153, and the last line of points_to_crowns,
+ * :239).  deeptreeattention_amd/stems.py: assign_np is the definition and the kernels equal it bit for bit.  Both tables
+ * are SORTED BY PLOT and every index below is a row of the sorted tables:
+ *   boxes:       double [n_boxes][4] (xmin, ymin, xmax, ymax) on the device; box_start: int [plots + 1] on the device, the
+ *                boxes of plot p are the rows box_start[p] .. box_start[p + 1] - 1
+ *   points:      double [n_points][2] (x, y); point_plot: int [n_points], the plot code of every stem; point_start: int
+ *                [plots + 1] as box_start; height: double [n_points], NaN where not measured; chm: the same or NULL
+ * Stem i of plot p (all in double, every product, sum and difference rounded on its own, no FMA):
+ *   candidates:  the boxes j of plot p with xmin <= px <= xmax and ymin <= py <= ymax (closed; false with a NaN)
+ *   missing:     a stem without a candidate; its fallback box is (px - size, py - size, px + size, py + size) with the index
+ *                n_boxes + i, a candidate of every MISSING stem of plot p that lies in it
+ *   choice:      the candidate with the smallest d2 = (cx - px) * (cx - px) + (cy - py) * (cy - py), cx = (xmin + xmax) * 0.5,
+ *                cy = (ymin + ymax) * 0.5; a NaN d2 counts as +inf; the lowest index among equals
+ *   one stem per box, G = the stems with the same choice:  |G| = 1 keeps it.  Else S = the stems of G at the largest height
+ *                that is not NaN; if |S| > 1 and chm is given, S = those of S at the largest chm that is not NaN; the lowest
+ *                index of S is kept, and nobody if S is empty
+ *   choice_out:  long long [n_points], the chosen index or -1
+ *   status_out:  bytes: 0 dropped for a taller stem, 1 kept with a predicted box, 2 kept with a fallback box, 3 dropped, S is
+ *                empty, 4 no box: a coordinate that is not finite or a plot code outside 0 .. plots - 1
+ *   crowns_out:  double [n_points][4], the chosen box or NaN
+ * Three launches on `stream` (one stem per lane; the rows a workgroup's stems can meet are staged through LDS,
+ * DTA_STEMS_CHUNK at a time), no workspace beyond choice_out, no atomics; every output element is overwritten.  An entry of
+ * box_start / point_start is clamped into its table before use: nothing is read outside a table whatever the arrays hold.
+ * n_boxes == 0 is legal (every stem falls back; boxes must still not be NULL).  Refused on the host, before any launch: a
+ * null pointer other than chm; n_points < 1 or >= 2^31; n_boxes < 0 or >= 2^31; plots < 1; a size that is not finite or
+ * <= 0. */
+#define DTA_STEMS_CHUNK 1024                /* boxes or stems staged through LDS at a time */
+int dta_stems_assign(const double* boxes, const int* box_start, long long n_boxes, const double* points, const int* point_plot,
+                     const int* point_start, const double* height, const double* chm, long long n_points, int plots,
+                     double size, long long* choice_out, unsigned char* status_out, double* crowns_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
