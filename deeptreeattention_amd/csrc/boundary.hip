@@ -29,15 +29,6 @@ constexpr int BD_LANE_COLS = 4;                          // the raster kernel: c
 constexpr int BD_ROW_COLS = BD_LANE_COLS * BD_THREADS;   // ... and columns of one row per workgroup
 static_assert(BD_EDGE_CHUNK % BD_THREADS == 0, "the raster kernel looks at BD_EDGE_CHUNK / BD_THREADS edges per lane and chunk");
 
-// x * y rounded to float64 on its own: the empty asm makes the product opaque, so no later subtraction is fused into it
-__device__ __forceinline__ double mul_rounded(double x, double y) {
-  double p = x * y;
-  asm("" : "+v"(p));
-  return p;
-}
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN, +-inf
-
 struct Bbox { double xmin, ymin, xmax, ymax; };
 
 __device__ __forceinline__ double wave_min_d(double v) {

@@ -160,6 +160,13 @@ __device__ __forceinline__ float mul_rounded(float x, float s) {
   asm volatile("" : "+v"(p));
   return p;
 }
+// the float64 one (boundary.hip, stems.hip: edge and distance tests that follow their definitions operation by operation)
+__device__ __forceinline__ double mul_rounded(double x, double y) {
+  double p = x * y;
+  asm("" : "+v"(p));
+  return p;
+}
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN, +-inf
 // a raw raster / crop element as float32
 __device__ __forceinline__ float to_f(float v) { return v; }
 __device__ __forceinline__ float to_f(short v) { return (float)v; }

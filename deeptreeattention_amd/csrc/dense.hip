@@ -16,6 +16,7 @@
 // All are bandwidth-bound copies or short reductions: no float atomics, fixed summation order, bit-identical reruns.
 #include "../../include/dta_hip.h"
 #include "kernels.h"
+#include "top2_dev.h"
 #include "walk_dev.h"
 
 // k_raster_normalise scales through common.h's minmax_* helpers, as k_preprocess_crops* (preprocess.hip) and
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256) void k_gather_tiles(GatherArgs a) {
 
 // One workgroup per crown.  A thread owns classes t, t + 256, ...: it adds the crown's rows of that class in row order
 // (one float32 accumulator, no atomics, no tree: the order is the definition, dense.crown_reduce_np) and divides by the
-// count.  Top-2 of the mean as k_softmax_top2 takes it (strictly greater replaces: ties go to the lower class).
+// count.  Top-2 of the mean as every epilogue takes it (top2_take, top2_dev.h: ties go to the lower class).
 __global__ __launch_bounds__(256) void k_crown_reduce(CrownArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int k = blockIdx.x, t = threadIdx.x, classes = a.classes;
@@ -224,8 +225,7 @@ __global__ __launch_bounds__(256) void k_crown_reduce(CrownArgs a) {
     for (; r < cnt; ++r) acc += src[(size_t)r * classes];
     const float mv = acc / fc;
     mean[c] = mv;
-    if (mv > b1) { b2 = b1; i2 = i1; b1 = mv; i1 = c; }
-    else if (mv > b2) { b2 = mv; i2 = c; }
+    top2_take(mv, c, b1, i1, b2, i2);
   }
   // the threads' (best, second) pairs, merged by one thread in thread order (= ascending class within equal values)
   float* cs = sm;
@@ -286,26 +286,11 @@ __global__ __launch_bounds__(64 * BLEND_CE_MULTI_MAX) void k_crown_resolve(Crown
         }
         for (; r < cnt; ++r) acc += src[(size_t)r * classes];
         mv = acc / fc;
-        if (mv > b1) { b2 = b1; i2 = i1; b1 = mv; i1 = c; }
-        else if (mv > b2) { b2 = mv; i2 = c; }
+        top2_take(mv, c, b1, i1, b2, i2);
       }
       if (mean) mean[c] = mv;               // an empty crown: mean 0, labels -1, scores 0
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
-      const int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
-      auto better = [](float a_, int ia, float b_, int ib) { return ia >= 0 && (ib < 0 || a_ > b_ || (a_ == b_ && ia < ib)); };
-      float n1, n2; int j1, j2;
-      if (better(b1, i1, ob1, oi1)) {
-        n1 = b1; j1 = i1;
-        if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
-      } else {
-        n1 = ob1; j1 = oi1;
-        if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
-      }
-      b1 = n1; i1 = j1; b2 = n2; i2 = j2;
-    }
+    top2_wave_merge(b1, i1, b2, i2);
     const float t1 = i1 < 0 ? 0.f : b1, t2 = i2 < 0 ? 0.f : b2;
     if (lane == 0) {
       L.top_idx[2 * (size_t)k] = i1; L.top_idx[2 * (size_t)k + 1] = i2;

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include "kernels.h"
 #include "ce_dev.h"
+#include "top2_dev.h"
 #include "walk_dev.h"
 
 namespace dta {
@@ -511,20 +512,10 @@ int launch_blend(const BlendArgs& a, hipStream_t st) {
 // Year ensemble: scores = mean over the years' last-head scores (reference src/models/year.py:33).
 // ------------------------------------------------------------------------------------------------
 __global__ void k_mean_scores(MeanArgs a) {
-  float kept = 0.f;
-  unsigned use = 0u;                                  // bit k: source k takes part (a bit mask: an indexed array would live in scratch)
-#pragma unroll
-  for (int k = 0; k < MAXG; ++k)
-    if (k < a.n && (!a.gate || a.gate[k] > 0.f)) { use |= 1u << k; kept += 1.f; }
-  const float inv = 1.f / kept;                       // nothing kept: inf, and 0 * inf = NaN below -- an empty mean
-  if (a.kept && blockIdx.x == 0 && threadIdx.x == 0) { a.kept[0] = kept; a.kept[1] = inv; }
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXG; ++k)
-      if ((use >> k) & 1u) acc += a.src[k][i];         // (selected, not multiplied: a skipped year's scores may be anything)
-    a.dst[i] = acc * inv;
-  }
+  const KeptSources ks = kept_sources(a.n, a.gate);
+  if (a.kept && blockIdx.x == 0 && threadIdx.x == 0) { a.kept[0] = ks.kept; a.kept[1] = ks.inv; }
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x)
+    a.dst[i] = kept_mean(ks, a.src, i);
 }
 // flags[y] = 1 when year y's tensor has a non-zero element (NaN counts), else 0: the reference's `x.sum() == 0` test of a
 // missing year (year.py:27) for the non-negative crops its loader produces (a sum of non-negative floats is zero exactly
@@ -708,189 +699,35 @@ int launch_weighted_ce(const CeArgs& a, hipStream_t st) {
 // Inference epilogue: softmax over classes (reference multi_stage.py:302,315; main.py:190) plus the top-2 labels and
 // scores main.py:192-205 extracts on the host.  One wave per row.
 // ------------------------------------------------------------------------------------------------
+// (the row itself -- max, sum of exponentials, probabilities, top-2 and its tie rule -- is softmax_top2_row_body, top2_dev.h)
 __global__ __launch_bounds__(256) void k_softmax_top2(const float* logits, int B, int classes, float* probs,
                                                       long long* top_idx, float* top_score) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;
   const float* z = logits + (size_t)row * classes;
-  float mx = -3.4e38f;
-  for (int n = lane; n < classes; n += 64) mx = fmaxf(mx, z[n]);
-  mx = wave_max(mx);
-  float se = 0.f;
-  for (int n = lane; n < classes; n += 64) se += __expf(z[n] - mx);
-  se = wave_sum(se);
-  const float inv = 1.f / se;
-  float b1 = -1.f, b2 = -1.f;
-  int i1 = -1, i2 = -1;
-  for (int n = lane; n < classes; n += 64) {
-    float pr = __expf(z[n] - mx) * inv;
-    if (probs) probs[(size_t)row * classes + n] = pr;
-    if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = n; }
-    else if (pr > b2) { b2 = pr; i2 = n; }
-  }
-  // merge the per-lane (best, second) pairs across the wave; ties resolve to the lower class index (as torch.topk)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
-    int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
-    auto better = [](float a, int ia, float b, int ib) { return a > b || (a == b && ia >= 0 && (ib < 0 || ia < ib)); };
-    float n1, n2; int j1, j2;
-    if (better(b1, i1, ob1, oi1)) {
-      n1 = b1; j1 = i1;
-      if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
-    } else {
-      n1 = ob1; j1 = oi1;
-      if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
-    }
-    b1 = n1; i1 = j1; b2 = n2; i2 = j2;
-  }
-  if (lane == 0) {
-    top_idx[row * 2] = i1; top_idx[row * 2 + 1] = i2;
-    top_score[row * 2] = b1; top_score[row * 2 + 1] = b2;
-  }
+  float* p = probs ? probs + (size_t)row * classes : nullptr;
+  const SoftmaxRow r = softmax_top2_row_body(
+      classes, lane, [&](int n) __attribute__((always_inline)) { return z[n]; },
+      [&](int n, float, float pr) __attribute__((always_inline)) { if (p) p[n] = pr; });
+  if (lane == 0) top2_store(top_idx, top_score, row, r.b1, r.i1, r.b2, r.i2);
+}
+// One level's row of the multi-stage epilogue: the scores are the mean over the level's kept sources, formed on the fly as
+// k_mean_scores forms it.  Every lane returns with the row's top-2 (r.i1, r.b1: the class and probability the walk needs).
+__device__ __forceinline__ SoftmaxRow softmax_top2_row(const SoftmaxLevel& a, int row, int lane) {
+  const KeptSources ks = kept_sources(a.nsrc, a.gate);
+  const size_t at = (size_t)row * a.classes;
+  const SoftmaxRow r = softmax_top2_row_body(
+      a.classes, lane, [&](int n) __attribute__((always_inline)) { return kept_mean(ks, a.src, at + n); },
+      [&](int n, float z, float pr) __attribute__((always_inline)) {
+        if (a.mean_out) a.mean_out[at + n] = z;
+        if (a.probs) a.probs[at + n] = pr;
+      });
+  if (lane == 0) top2_store(a.top_idx, a.top_score, row, r.b1, r.i1, r.b2, r.i2);
+  return r;
 }
 __global__ __launch_bounds__(256) void k_softmax_top2_multi(SoftmaxMulti m) {
-  const SoftmaxLevel& a = m.lv[blockIdx.y];
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= m.B) return;
-  const int classes = a.classes;
-  float kept = 0.f;
-  unsigned use = 0u;
-#pragma unroll
-  for (int k = 0; k < MAXG; ++k)
-    if (k < a.nsrc && (!a.gate || a.gate[k] > 0.f)) { use |= 1u << k; kept += 1.f; }
-  const float kinv = 1.f / kept;                      // nothing kept: inf, 0 * inf = NaN -- an empty mean, as k_mean_scores
-  auto zat = [&](int n) __attribute__((always_inline)) {
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXG; ++k)
-      if ((use >> k) & 1u) acc += a.src[k][(size_t)row * classes + n];
-    return acc * kinv;
-  };
-  // the first 256 classes of the row live in registers (four per lane); wider rows re-form the rest
-  float zc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; zc[k] = n < classes ? zat(n) : -3.4e38f; }
-  // visit this lane's classes in ascending order: the register-held ones statically indexed, then the re-formed tail
-  auto each = [&](auto&& f) __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; if (n < classes) f(n, zc[k]); }
-    for (int n = lane + 256; n < classes; n += 64) f(n, zat(n));
-  };
-  float mx = -3.4e38f;
-  each([&](int, float z) __attribute__((always_inline)) { mx = fmaxf(mx, z); });
-  mx = wave_max(mx);
-  float se = 0.f;
-  each([&](int, float z) __attribute__((always_inline)) { se += __expf(z - mx); });
-  se = wave_sum(se);
-  const float inv = 1.f / se;
-  float b1 = -1.f, b2 = -1.f;
-  int i1 = -1, i2 = -1;
-#define DTA_ROW_OUT(n_, z_)                                                                      \
-  {                                                                                              \
-    const int nn = (n_);                                                                         \
-    const float zz = (z_);                                                                       \
-    if (a.mean_out) a.mean_out[(size_t)row * classes + nn] = zz;                                 \
-    const float pr = __expf(zz - mx) * inv;                                                      \
-    if (a.probs) a.probs[(size_t)row * classes + nn] = pr;                                       \
-    if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = nn; }                                         \
-    else if (pr > b2) { b2 = pr; i2 = nn; }                                                      \
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; if (n < classes) DTA_ROW_OUT(n, zc[k]) }
-  for (int n = lane + 256; n < classes; n += 64) DTA_ROW_OUT(n, zat(n))
-#undef DTA_ROW_OUT
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
-    int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
-    auto better = [](float a_, int ia, float b_, int ib) { return a_ > b_ || (a_ == b_ && ia >= 0 && (ib < 0 || ia < ib)); };
-    float n1, n2; int j1, j2;
-    if (better(b1, i1, ob1, oi1)) {
-      n1 = b1; j1 = i1;
-      if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
-    } else {
-      n1 = ob1; j1 = oi1;
-      if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
-    }
-    b1 = n1; i1 = j1; b2 = n2; i2 = j2;
-  }
-  if (lane == 0) {
-    if (a.top_idx) { a.top_idx[row * 2] = i1; a.top_idx[row * 2 + 1] = i2; }
-    if (a.top_score) { a.top_score[row * 2] = b1; a.top_score[row * 2 + 1] = b2; }
-  }
-}
-// k_softmax_top2_multi's row, statement for statement (that kernel stays as it is: its code is the yardstick of
-// dta_multistage_predict), for the kernel below, whose waves need the row's top-1 afterwards: every lane returns with
-// the row's top-1 class and probability (i1, b1)
-__device__ __forceinline__ void softmax_top2_row(const SoftmaxLevel& a, int row, int lane, float& b1, int& i1) {
-  const int classes = a.classes;
-  float kept = 0.f;
-  unsigned use = 0u;
-#pragma unroll
-  for (int k = 0; k < MAXG; ++k)
-    if (k < a.nsrc && (!a.gate || a.gate[k] > 0.f)) { use |= 1u << k; kept += 1.f; }
-  const float kinv = 1.f / kept;                      // nothing kept: inf, 0 * inf = NaN -- an empty mean, as k_mean_scores
-  auto zat = [&](int n) __attribute__((always_inline)) {
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXG; ++k)
-      if ((use >> k) & 1u) acc += a.src[k][(size_t)row * classes + n];
-    return acc * kinv;
-  };
-  // the first 256 classes of the row live in registers (four per lane); wider rows re-form the rest
-  float zc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; zc[k] = n < classes ? zat(n) : -3.4e38f; }
-  // visit this lane's classes in ascending order: the register-held ones statically indexed, then the re-formed tail
-  auto each = [&](auto&& f) __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; if (n < classes) f(n, zc[k]); }
-    for (int n = lane + 256; n < classes; n += 64) f(n, zat(n));
-  };
-  float mx = -3.4e38f;
-  each([&](int, float z) __attribute__((always_inline)) { mx = fmaxf(mx, z); });
-  mx = wave_max(mx);
-  float se = 0.f;
-  each([&](int, float z) __attribute__((always_inline)) { se += __expf(z - mx); });
-  se = wave_sum(se);
-  const float inv = 1.f / se;
-  float b2 = -1.f;
-  int i2 = -1;
-  b1 = -1.f; i1 = -1;
-#define DTA_ROW_OUT(n_, z_)                                                                      \
-  {                                                                                              \
-    const int nn = (n_);                                                                         \
-    const float zz = (z_);                                                                       \
-    if (a.mean_out) a.mean_out[(size_t)row * classes + nn] = zz;                                 \
-    const float pr = __expf(zz - mx) * inv;                                                      \
-    if (a.probs) a.probs[(size_t)row * classes + nn] = pr;                                       \
-    if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = nn; }                                         \
-    else if (pr > b2) { b2 = pr; i2 = nn; }                                                      \
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int n = lane + 64 * k; if (n < classes) DTA_ROW_OUT(n, zc[k]) }
-  for (int n = lane + 256; n < classes; n += 64) DTA_ROW_OUT(n, zat(n))
-#undef DTA_ROW_OUT
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
-    int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
-    auto better = [](float a_, int ia, float b_, int ib) { return a_ > b_ || (a_ == b_ && ia >= 0 && (ib < 0 || ia < ib)); };
-    float n1, n2; int j1, j2;
-    if (better(b1, i1, ob1, oi1)) {
-      n1 = b1; j1 = i1;
-      if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
-    } else {
-      n1 = ob1; j1 = oi1;
-      if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
-    }
-    b1 = n1; i1 = j1; b2 = n2; i2 = j2;
-  }
-  if (lane == 0) {
-    if (a.top_idx) { a.top_idx[row * 2] = i1; a.top_idx[row * 2 + 1] = i2; }
-    if (a.top_score) { a.top_score[row * 2] = b1; a.top_score[row * 2 + 1] = b2; }
-  }
+  if (row < m.B) softmax_top2_row(m.lv[blockIdx.y], row, lane);
 }
 // (the hierarchy walk itself, hierarchy_walk, is in walk_dev.h: k_crown_resolve of dense.hip walks the same table)
 // k_softmax_top2_multi with the levels of a crop as the WAVES of one workgroup (wave = level, workgroup = crop) instead of
@@ -900,9 +737,8 @@ __global__ __launch_bounds__(64 * BLEND_CE_MULTI_MAX) void k_softmax_top2_ensemb
   __shared__ int s_cls[BLEND_CE_MULTI_MAX];
   __shared__ float s_score[BLEND_CE_MULTI_MAX];
   const int lane = threadIdx.x & 63, lvl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), row = blockIdx.x;
-  float b1; int i1;
-  softmax_top2_row(m.lv[lvl], row, lane, b1, i1);
-  if (lane == 0) { s_cls[lvl] = i1; s_score[lvl] = b1; }
+  const SoftmaxRow r = softmax_top2_row(m.lv[lvl], row, lane);
+  if (lane == 0) { s_cls[lvl] = r.i1; s_score[lvl] = r.b1; }
   __syncthreads();
   if (threadIdx.x >= 64) return;
   const bool mine = lane < m.n;
@@ -962,93 +798,31 @@ int launch_softmax_top2(const float* logits, int B, int classes, float* probs, l
 __device__ __forceinline__ void eval_row(const EvalLevel& e, int row, int lane, int* s_cnt) {
   const BlendCeArgs& a = e.ce;
   const int classes = a.classes;
-  float kept = 0.f;
-  unsigned use = 0u;
-#pragma unroll
-  for (int k = 0; k < MAXG; ++k)
-    if (k < a.nsrc && (!a.src_gate || a.src_gate[k] > 0.f)) { use |= 1u << k; kept += 1.f; }
-  const float kinv = 1.f / kept;                      // nothing kept: inf, 0 * inf = NaN -- an empty mean, as k_mean_scores
+  const KeptSources ks = kept_sources(a.nsrc, a.src_gate);
   const bool direct = a.nsrc == 0;                    // single-model use: the scores are one [B][classes] array
-  auto zat = [&](int n) __attribute__((always_inline)) {
-    if (direct) return a.spec[(size_t)row * classes + n];
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXG; ++k)
-      if ((use >> k) & 1u) acc += a.src[k][(size_t)row * classes + n];
-    return acc * kinv;
-  };
-  // the first 256 classes of the row live in registers (four per lane, as named scalars: blend_ce_body below brings small
-  // arrays of its own, and one more here is what the compiler no longer keeps in registers); wider rows re-form the rest
-  const float z0 = lane < classes ? zat(lane) : -3.4e38f, z1 = lane + 64 < classes ? zat(lane + 64) : -3.4e38f;
-  const float z2 = lane + 128 < classes ? zat(lane + 128) : -3.4e38f, z3 = lane + 192 < classes ? zat(lane + 192) : -3.4e38f;
-  auto each = [&](auto&& f) __attribute__((always_inline)) {      // this lane's classes in ascending order
-    if (lane < classes) f(lane, z0);
-    if (lane + 64 < classes) f(lane + 64, z1);
-    if (lane + 128 < classes) f(lane + 128, z2);
-    if (lane + 192 < classes) f(lane + 192, z3);
-    for (int n = lane + 256; n < classes; n += 64) f(n, zat(n));
-  };
-  float mx = -3.4e38f;
-  each([&](int, float z) __attribute__((always_inline)) { mx = fmaxf(mx, z); });
-  mx = wave_max(mx);
-  float se = 0.f;
-  each([&](int, float z) __attribute__((always_inline)) { se += __expf(z - mx); });
-  se = wave_sum(se);
-  const float inv = 1.f / se;
-  float b1 = -1.f, b2 = -1.f;
-  int i1 = -1, i2 = -1;
-  // (a macro, as in k_softmax_top2_multi: through a lambda's by-reference captures the compare-and-replace below turns into
-  //  stores through a selected pointer, and b1 / b2 / i1 / i2 would live in the private segment)
-#define DTA_EVAL_ROW_OUT(n_, z_)                                                                 \
-  {                                                                                              \
-    const int nn = (n_);                                                                         \
-    const float pr = __expf((z_) - mx) * inv;                                                    \
-    if (e.probs) e.probs[(size_t)row * classes + nn] = pr;                                       \
-    if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = nn; }                                         \
-    else if (pr > b2) { b2 = pr; i2 = nn; }                                                      \
-  }
-  if (lane < classes) DTA_EVAL_ROW_OUT(lane, z0)
-  if (lane + 64 < classes) DTA_EVAL_ROW_OUT(lane + 64, z1)
-  if (lane + 128 < classes) DTA_EVAL_ROW_OUT(lane + 128, z2)
-  if (lane + 192 < classes) DTA_EVAL_ROW_OUT(lane + 192, z3)
-  for (int n = lane + 256; n < classes; n += 64) DTA_EVAL_ROW_OUT(n, zat(n))
-#undef DTA_EVAL_ROW_OUT
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
-    int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
-    auto better = [](float a_, int ia, float b_, int ib) { return a_ > b_ || (a_ == b_ && ia >= 0 && (ib < 0 || ia < ib)); };
-    float n1, n2; int j1, j2;
-    if (better(b1, i1, ob1, oi1)) {
-      n1 = b1; j1 = i1;
-      if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
-    } else {
-      n1 = ob1; j1 = oi1;
-      if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
-    }
-    b1 = n1; i1 = j1; b2 = n2; i2 = j2;
-  }
-  if (lane == 0) {
-    if (e.top_idx) { e.top_idx[row * 2] = i1; e.top_idx[row * 2 + 1] = i2; }
-    if (e.top_score) { e.top_score[row * 2] = b1; e.top_score[row * 2 + 1] = b2; }
-  }
+  const size_t at = (size_t)row * classes;
+  auto zat = [&](int n) __attribute__((always_inline)) { return direct ? a.spec[at + n] : kept_mean(ks, a.src, at + n); };
+  const SoftmaxRow r = softmax_top2_row_body(classes, lane, zat, [&](int n, float, float pr) __attribute__((always_inline)) {
+    if (e.probs) e.probs[at + n] = pr;
+  });
+  if (lane == 0) top2_store(e.top_idx, e.top_score, row, r.b1, r.i1, r.b2, r.i2);
   const long long y = a.labels[row];
-  const bool ok = y >= 0 && y < classes && i1 >= 0;
+  const bool ok = y >= 0 && y < classes && r.i1 >= 0;
   if (!ok) return;                                    // (wave-uniform: y and the merged top-1 are the same on every lane)
   // the label's rank: how many classes beat its probability (a tie goes to the lower index) -- the same __expf(z - mx) * inv
-  // on the same operands as above, so the label is rank 0 exactly when it is top_idx[0]
-  const float py = __expf(zat((int)y) - mx) * inv;
+  // on the same operands as in the row body, so the label is rank 0 exactly when it is top_idx[0]
+  const float py = __expf(zat((int)y) - r.mx) * r.inv;
   int rank = 0;
-  each([&](int n, float z) __attribute__((always_inline)) {
-    const float pr = __expf(z - mx) * inv;
+  softmax_row_each(r, classes, lane, zat, [&](int n, float z) __attribute__((always_inline)) {
+    const float pr = __expf(z - r.mx) * r.inv;
     if (pr > py || (pr == py && n < (int)y)) rank += 1;
   });
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o);
   if (lane == 0) {
-    if (e.confusion) atomicAdd(reinterpret_cast<unsigned long long*>(e.confusion) + (size_t)y * classes + i1, 1ull);
+    if (e.confusion) atomicAdd(reinterpret_cast<unsigned long long*>(e.confusion) + (size_t)y * classes + r.i1, 1ull);
     atomicAdd(&s_cnt[0], 1);
-    if (i1 == (int)y) atomicAdd(&s_cnt[1], 1);
+    if (r.i1 == (int)y) atomicAdd(&s_cnt[1], 1);
     if (rank < e.top_k) atomicAdd(&s_cnt[2], 1);
   }
 }

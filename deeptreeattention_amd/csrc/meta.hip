@@ -14,6 +14,7 @@
 
 #include "../../include/dta_hip.h"
 #include "kernels.h"
+#include "top2_dev.h"
 
 using namespace dta;
 
@@ -397,7 +398,7 @@ struct FuseArgs {
 // grid ceil(B / 8), 256 threads.  Phase 1: thread = class (c = t, t + 256, ...), eight float32 accumulators (one per row of
 // the tile) that start at T[site][c] and take k ascending: Wh[k][c] comes coalesced out of L2 (independent of the
 // accumulators, so the loads run ahead), the rows' HSI scores are LDS broadcasts of four k at a time.  Phase 2: wave = row
-// (two rows per wave), k_softmax_top2's arithmetic and tie rule on the tile's fused scores in LDS.
+// (two rows per wave), k_softmax_top2's row body (softmax_top2_row_body, top2_dev.h) on the tile's fused scores in LDS.
 // A row's instructions do not depend on its place in the tile or on the batch size: its bits do not either.
 // dynamic LDS: hs [8][Cp] | sc [8][Cp], Cp = C rounded up to 4
 __global__ __launch_bounds__(256) void k_meta_fuse_top2(FuseArgs a) {
@@ -459,49 +460,18 @@ __global__ __launch_bounds__(256) void k_meta_fuse_top2(FuseArgs a) {
         if (a.out) a.out[(size_t)row * C + n] = 0.f;
         if (a.probs) a.probs[(size_t)row * C + n] = 0.f;
       }
-      if (lane == 0) {
-        a.top_idx[(size_t)row * 2] = -1; a.top_idx[(size_t)row * 2 + 1] = -1;
-        a.top_score[(size_t)row * 2] = 0.f; a.top_score[(size_t)row * 2 + 1] = 0.f;
-      }
+      if (lane == 0) top2_store(a.top_idx, a.top_score, row, 0.f, -1, 0.f, -1);
       continue;
     }
     const float* z = sc + r * Cp;
-    float mx = -3.4e38f;
-    for (int n = lane; n < C; n += 64) mx = fmaxf(mx, z[n]);
-    mx = wave_max(mx);
-    float se = 0.f;
-    for (int n = lane; n < C; n += 64) se += __expf(z[n] - mx);
-    se = wave_sum(se);
-    const float inv = 1.f / se;
-    float b1 = -1.f, b2 = -1.f;
-    int i1 = -1, i2 = -1;
-    for (int n = lane; n < C; n += 64) {
-      const float zn = z[n], pr = __expf(zn - mx) * inv;
-      if (a.out) a.out[(size_t)row * C + n] = zn;
-      if (a.probs) a.probs[(size_t)row * C + n] = pr;
-      if (pr > b1) { b2 = b1; i2 = i1; b1 = pr; i1 = n; }
-      else if (pr > b2) { b2 = pr; i2 = n; }
-    }
-    // the lanes' (best, second) pairs merged across the wave as k_softmax_top2 does: ties go to the lower class
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob1 = __shfl_xor(b1, o), ob2 = __shfl_xor(b2, o);
-      const int oi1 = __shfl_xor(i1, o), oi2 = __shfl_xor(i2, o);
-      auto better = [](float x, int ix, float y, int iy) { return x > y || (x == y && ix >= 0 && (iy < 0 || ix < iy)); };
-      float n1, n2; int j1, j2;
-      if (better(b1, i1, ob1, oi1)) {
-        n1 = b1; j1 = i1;
-        if (better(b2, i2, ob1, oi1)) { n2 = b2; j2 = i2; } else { n2 = ob1; j2 = oi1; }
-      } else {
-        n1 = ob1; j1 = oi1;
-        if (better(b1, i1, ob2, oi2)) { n2 = b1; j2 = i1; } else { n2 = ob2; j2 = oi2; }
-      }
-      b1 = n1; i1 = j1; b2 = n2; i2 = j2;
-    }
-    if (lane == 0) {
-      a.top_idx[(size_t)row * 2] = i1; a.top_idx[(size_t)row * 2 + 1] = i2;
-      a.top_score[(size_t)row * 2] = b1; a.top_score[(size_t)row * 2 + 1] = b2;
-    }
+    const size_t at = (size_t)row * C;
+    const SoftmaxRow sr = softmax_top2_row_body(
+        C, lane, [&](int n) __attribute__((always_inline)) { return z[n]; },
+        [&](int n, float zn, float pr) __attribute__((always_inline)) {
+          if (a.out) a.out[at + n] = zn;
+          if (a.probs) a.probs[at + n] = pr;
+        });
+    if (lane == 0) top2_store(a.top_idx, a.top_score, row, sr.b1, sr.i1, sr.b2, sr.i2);
   }
 }
 

@@ -23,7 +23,7 @@
 #include <cmath>
 
 // no fused multiply-add in this file: (cx - px) * (cx - px) + (cy - py) * (cy - py) is the definition's operations one by
-// one (hipcc contracts by default; see mul_rounded)
+// one (hipcc contracts by default; see mul_rounded in common.h)
 #pragma clang fp contract(off)
 
 namespace dta {
@@ -31,15 +31,6 @@ namespace dta {
 constexpr int ST_THREADS = 256;
 constexpr int ST_WAVES = ST_THREADS / 64;
 constexpr int ST_CHUNK = DTA_STEMS_CHUNK;
-
-// x * y rounded to float64 on its own: the empty asm makes the product opaque, so no later addition is fused into it
-__device__ __forceinline__ double mul_rounded(double x, double y) {
-  double p = x * y;
-  asm("" : "+v"(p));
-  return p;
-}
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN, +-inf
 
 __device__ __forceinline__ int clamp_row(int v, int rows) { return v < 0 ? 0 : (v > rows ? rows : v); }
 
