@@ -27,6 +27,9 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.stems      <->  src/generate.py process_plot + create_boxes + choose_box: which crown box a
                                      field-measured stem gets (join, fallback box, nearest centre) and which stem a box
                                      keeps (the tallest), all plots of a site in one chain of three launches
+    deeptreeattention_amd.treedata   <->  src/data.py TreeDataset + multi_stage.py create_datasets' five of them: the crops
+                                     of a whole data set resident once, a level as rows and labels, a shuffled order per
+                                     level and epoch, and every level x year batch of a train step in one launch
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.
@@ -39,8 +42,9 @@ from .dense import DenseRaster, window_origins, predict_windows, predict_map  # 
 from .dense import predict_windows_multistage, predict_map_multistage, crown_resolve  # noqa: F401
 from .dense import predict_windows_metadata, predict_map_metadata  # noqa: F401
 from .dense import crop_boxes, predict_crops, predict_crops_multistage, predict_crops_metadata  # noqa: F401
+from .treedata import CropPool, PoolView, LevelViews, epoch_order_np  # noqa: F401
 
-__all__ = ["Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
+__all__ = ["CropPool", "PoolView", "LevelViews", "epoch_order_np","Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
            "validate", "validate_multistage", "DenseRaster", "window_origins", "predict_windows", "predict_map",
            "predict_windows_multistage", "predict_map_multistage", "crown_resolve",
            "crop_boxes", "predict_crops", "predict_crops_multistage", "predict_crops_metadata"]

@@ -102,6 +102,15 @@ BOUNDARY_MAX_EDGES = 1 << 20   # DTA_BOUNDARY_MAX_EDGES
 SPLIT_MAX_SPECIES = 256   # DTA_SPLIT_MAX_SPECIES
 SPLIT_MAX_CANDIDATES = 4096   # DTA_SPLIT_MAX_CANDIDATES
 STEMS_CHUNK = 1024   # DTA_STEMS_CHUNK
+EPOCH_ORDER_MAX_N = 1 << 20   # DTA_EPOCH_ORDER_MAX_N
+EPOCH_ORDER_STREAM = 16   # DTA_EPOCH_ORDER_STREAM
+EPOCH_ORDER_MAX_LEVEL_ID = 64   # DTA_EPOCH_ORDER_MAX_LEVEL_ID
+
+
+class PoolLevel(C.Structure):       # dta_pool_level
+    _fields_ = [("order", C.c_void_p), ("rows", C.c_void_p), ("labels", C.c_void_p), ("n", C.c_longlong),
+                ("start", C.c_longlong), ("count", C.c_int), ("flip", C.c_int), ("out_labels", C.c_void_p),
+                ("out_rows", C.c_void_p)]
 
 
 class ReflectanceDesc(C.Structure):     # dta_reflectance_desc
@@ -385,6 +394,14 @@ def lib():
         L.dta_stems_assign.restype = C.c_int
         L.dta_stems_assign.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_longlong, C.c_int, C.c_double, vp, vp, vp,
                                        vp]
+        # the resident training set: every level's epoch order, and every level x year batch of a step, one launch each
+        # (treedata.hip); n, level_ids, orders, lv and outs are HOST arrays
+        L.dta_epoch_order.restype = C.c_int
+        L.dta_epoch_order.argtypes = [C.c_int, c_ll_p, C.POINTER(C.c_int), C.c_ulonglong, C.c_ulonglong,
+                                      C.POINTER(C.c_void_p), vp]
+        L.dta_pool_batches.restype = C.c_int
+        L.dta_pool_batches.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PoolLevel),
+                                       C.POINTER(C.c_void_p), vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -1326,19 +1326,30 @@ class MultiStageTrainer:
                     return False
         return True
 
-    def training_step_all(self, batch, batch_idx=0, present=None):
+    def training_step_all(self, batch, batch_idx=0, present=None, year_flags=None):
         """One optimisation step of EVERY level on its batch: batch[l] = (individual, {"HSI": [year tensors]}, labels) as
         Lightning hands them to MultiStage.training_step (multi_stage.py:277-288, once per optimizer_idx).  Returns the
         list of per-level losses (fresh 0-d device tensors).  The levels x kept-years networks run as the groups of ONE
         launch chain -- one forward, ONE loss launch over the levels, one backward, one optimizer launch per 16 parameter
         segments, each level with its own class weights and learning rate (dta_multistage_*); results are those of
         training_step(batch, ., l) for l = 0, 1, ... in turn.  present: None (missing years decided on the device, no host
-        synchronisation), or one list of booleans per level.  Steps the levels one after the other when they cannot share a
-        launch chain (different batch sizes or shapes, more than 16 kept networks, data-parallel trainers, levels whose
-        betas / eps / keep_grads differ)."""
+        synchronisation), or one list of booleans per level.  year_flags (float32, one entry per network, level-major, on
+        the device; instead of `present`): the networks' 0/1 flags as dta_year_flags would set them, from whoever wrote the
+        batches (treedata.LevelViews.batches sets them while it gathers) -- used as the gate as they are, and
+        dta_year_flags is not launched; MultiStagePredictor.__call__(year_flags=) has the same contract.  Steps the levels
+        one after the other when they cannot share a launch chain (different batch sizes or shapes, more than 16 kept
+        networks, data-parallel trainers, levels whose betas / eps / keep_grads differ); that path ignores year_flags and
+        decides on the device as it does for present=None."""
         nl = len(self.levels)
         if len(batch) != nl:
             raise ValueError("expected one batch per level ({}), got {}".format(nl, len(batch)))
+        if year_flags is not None:
+            if present is not None:
+                raise ValueError("pass `present` (host booleans) or `year_flags` (device flags), not both")
+            n_nets = sum(len(t.years) for t in self.levels)
+            if (not isinstance(year_flags, torch.Tensor) or year_flags.dtype != torch.float32 or tuple(year_flags.shape) != (n_nets,)
+                    or year_flags.device != self.levels[0].device or not year_flags.is_contiguous()):
+                raise ValueError("year_flags must be a contiguous float32 [{}] tensor on {}".format(n_nets, self.levels[0].device))
         if present is not None and len(present) != nl:
             raise ValueError("present: one list of year flags per level")
         xs_levels = [[H._check_input(x) for x in b[1]["HSI"]] for b in batch]
@@ -1388,7 +1399,9 @@ class MultiStageTrainer:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self._ws_key = ws_key
         gate = None
-        if present is None:
+        if year_flags is not None:
+            gate = year_flags           # set by whoever wrote the batches: nothing is read back
+        elif present is None:
             # the reference's missing-year test (year.py:27) for every network of the step in one launch, on the device
             if self._gate_banks is None or self._gate_banks.shape[1] != n:
                 self._gate_banks = torch.zeros(2, n, dtype=torch.float32, device=dev)
@@ -1440,7 +1453,7 @@ class MultiStageTrainer:
             arr = (_lib.AdamSegment * len(part))(*part)
             _lib.check(L.dta_adam_step_multi(len(part), arr, 0.0, t0.betas[0], t0.betas[1], t0.eps, t0.sync.grad_scale,
                                              0 if t0.keep_grads else 1, st), "dta_adam_step_multi")
-        self._live = live      # inputs and labels stay referenced until the step's launches are enqueued
+        self._live = (live, year_flags)      # inputs, labels and flags stay referenced until the step's launches are enqueued
         return [t.loss for t in self.levels]
 
     def training_step(self, batch, batch_idx, optimizer_idx, present=None):

@@ -212,7 +212,9 @@ def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128,
     level's own validation loader (multi_stage.py:231-246, :290-304), `val_loss/dataloader_idx_{level}` = mean of its batch
     losses, and one plateau scheduler per level monitoring it (multi_stage.py:258-275).
     trainer: engine.MultiStageTrainer; train_data / val_data: one SyntheticTreeDataset(years=...) (or anything with
-    `.loader(batch_size, shuffle, seed)`) per level; schedulers: one PlateauScheduler per level (on `trainer.levels[l]`) or
+    `.loader(batch_size, shuffle, seed)`) per level, or a treedata.LevelViews -- the levels as views of one resident crop
+    pool: an epoch is then `train_data.batches(...)`, one gather launch per step, whose year flags go to
+    `training_step_all(year_flags=)` so that no batch is read back; schedulers: one PlateauScheduler per level (on `trainer.levels[l]`) or
     None.  Returns a list of {"epoch", "train_loss": [...], "val_loss": [...], "lr": [...]} records.
     metrics=True: the validation half is `validate_multistage` (all levels of a validation batch in one launch chain);
     `val_loss` is then weighted by batch size, the schedulers monitor that, and the record gains "val_metrics" (per level)."""
@@ -221,14 +223,22 @@ def fit_multistage(trainer, train_data, val_data=None, epochs=1, batch_size=128,
     if len(train_data) != nl or (val_data is not None and len(val_data) != nl):
         raise ValueError("one dataset per level ({})".format(nl))
     history = []
+    from .treedata import LevelViews
     for epoch in range(int(epochs)):
-        loaders = [list(d.loader(batch_size, shuffle, seed=epoch)) for d in train_data]
-        steps = max(len(b) for b in loaders)
         sums = [[] for _ in range(nl)]
-        for i in range(steps):
-            batch = [b[i % len(b)] for b in loaders]               # shorter loaders cycle ("max_size_cycle")
-            for l, loss in enumerate(trainer.training_step_all(batch, i)):
-                sums[l].append(loss.reshape(()))
+        if isinstance(train_data, LevelViews):
+            # views of one resident pool: every level x year batch of a step is one launch, which also sets the year flags
+            # (the same batches, in the same order, as the views' own loaders give below)
+            for i, (batch, flags) in enumerate(train_data.batches(batch_size, shuffle, seed=epoch)):
+                for l, loss in enumerate(trainer.training_step_all(batch, i, year_flags=flags)):
+                    sums[l].append(loss.reshape(()))
+        else:
+            loaders = [list(d.loader(batch_size, shuffle, seed=epoch)) for d in train_data]
+            steps = max(len(b) for b in loaders)
+            for i in range(steps):
+                batch = [b[i % len(b)] for b in loaders]               # shorter loaders cycle ("max_size_cycle")
+                for l, loss in enumerate(trainer.training_step_all(batch, i)):
+                    sums[l].append(loss.reshape(()))
         rec = {"epoch": epoch, "train_loss": [float(torch.stack(s).mean()) for s in sums], "val_loss": None}
         if val_data is not None and metrics:
             rec["val_metrics"] = validate_multistage(trainer, val_data, batch_size)

@@ -1026,6 +1026,59 @@ int dta_stems_assign(const double* boxes, const int* box_start, long long n_boxe
                      const int* point_start, const double* height, const double* chm, long long n_points, int plots,
                      double size, long long* choice_out, unsigned char* status_out, double* crowns_out, void* stream);
 
+/* ---- The resident training set: the crops of a whole data set once on the device, a shuffled order per level and epoch,
+ * and the batches of every level x year of a train step in one launch (the reference's TreeDataset, src/data.py:239-310,
+ * five of them over the same individuals in src/models/multi_stage.py:82-219).  deeptreeattention_amd/treedata.py:
+ * epoch_order_np and batch_np are the definitions and the kernels equal them bit for bit.
+ *
+ * dta_epoch_order: the order of `levels` (1..DTA_MAX_LEVELS) views in ONE launch.  n: HOST array, the entries of each view,
+ * 1..DTA_EPOCH_ORDER_MAX_N; level_ids: HOST array of the levels' stream numbers, each 0..DTA_EPOCH_ORDER_MAX_LEVEL_ID - 1,
+ * or NULL for 0, 1, ...; orders: HOST array of device pointers, int [n[l]] each.  Entry i of level l has the key
+ *   key_i = mix(((epoch * n[l] + i) mod 2^64) * 0x9E3779B97F4A7C15 + mix(seed * 0x9E3779B97F4A7C15 + S + 1)) >> 32,
+ *   S = DTA_EPOCH_ORDER_STREAM + level_ids[l]          (mix as for dta_abundance_resample; streams 0 and 1 are its and
+ *                                                       dta_split_search's)
+ * and orders[l] holds the entries sorted ascending by (key_i, i): orders[l][#{j : (key_j, j) < (key_i, i)}] = i.  About
+ * n^2 compares per level (the keys stream through LDS, hashed on the way), which is what bounds n: 2^20 entries are 1.1e12
+ * compares.  No atomics, every element of a table written once.  Refused on the host, before the launch: a null n or orders
+ * or table, levels or a level id out of range, an n outside 1..DTA_EPOCH_ORDER_MAX_N. */
+#define DTA_EPOCH_ORDER_MAX_N 1048576
+#define DTA_EPOCH_ORDER_STREAM 16
+#define DTA_EPOCH_ORDER_MAX_LEVEL_ID 64
+int dta_epoch_order(int levels, const long long* n, const int* level_ids, unsigned long long seed, unsigned long long epoch,
+                    int* const* orders, void* stream);
+/* dta_pool_batches: one step's batch of every level and year in ONE launch.
+ *   pool:   [pool_rows][years][bands][size][size] on the device, float32 (DTA_F32) or bf16 (DTA_BF16: widened exactly on
+ *           the way out); a missing (individual, year) slot holds zeros
+ *   lv:     HOST array of `levels` (1..DTA_MAX_LEVELS; levels * years <= DTA_MAX_YEARS networks) entries.  Position p
+ *           (0 .. count - 1) of level l brings view entry e = order[start + p] (order NULL: e = start + p) and pool row
+ *           rows[e]; flip != 0: the size * size pixels of every plane reversed, which is both training flips together
+ *           (src/augmentation.py:13-14)
+ *   outs:   HOST array of levels * years device pointers, level-major: float32 [count_l][bands][size][size], 16-byte aligned
+ *   out_labels / out_rows of a level: long long [count]: labels[e] and rows[e] (labels and out_labels may both be NULL)
+ *   flags:  float [levels * years], level-major: ends as 1 where that batch has a non-zero element (NaN counts, -0.0 does
+ *           not), taken from the values on their way out, else stays 0.  The bank protocol of dta_gather_windows_years: flags
+ *           zero on entry; clear_next (the other bank) is zeroed for the next call, or NULL: flags is cleared here first.
+ *           Plain stores only: no atomics.
+ * Every read is guarded on the device: an order entry outside 0 .. n - 1 or a row outside 0 .. pool_rows - 1 writes an
+ * all-zero crop (and -1 for an entry that does not exist), so the call cannot read outside the pool or the tables whatever
+ * they hold.  Pure copies: reruns are bit-identical.  Refused on the host, before the launch: a null pool / lv / outs /
+ * flags / rows / out_rows / out; labels without out_labels or the reverse; a dtype other than the two; levels, years,
+ * pool_rows, bands or size out of range; a level with n < 1, start < 0, count < 1 or start + count > n; an out that is not
+ * 16-byte aligned. */
+typedef struct {
+  const int* order;           /* int [n] on the device (dta_epoch_order), or NULL: the identity */
+  const long long* rows;      /* [n] on the device: view entry -> pool row */
+  const long long* labels;    /* [n] on the device, or NULL */
+  long long n;                /* entries of the view */
+  long long start;            /* first position of this step's batch */
+  int count;                  /* crops of this step's batch */
+  int flip;                   /* both training flips */
+  long long* out_labels;      /* [count] or NULL */
+  long long* out_rows;        /* [count] */
+} dta_pool_level;
+int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years, int bands, int size, int levels,
+                     const dta_pool_level* lv, float* const* outs, float* flags, float* clear_next, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
