@@ -30,6 +30,9 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.treedata   <->  src/data.py TreeDataset + multi_stage.py create_datasets' five of them: the crops
                                      of a whole data set resident once, a level as rows and labels, a shuffled order per
                                      level and epoch, and every level x year batch of a train step in one launch
+    deeptreeattention_amd.levels     <->  src/models/multi_stage.py MultiStage.__init__ + create_datasets: which individuals
+                                     each of the five levels trains on and in what order, the level labels, num_classes and
+                                     the loss weights, from one resident integer table in a chain of at most four launches
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

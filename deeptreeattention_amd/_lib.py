@@ -113,6 +113,30 @@ class PoolLevel(C.Structure):       # dta_pool_level
                 ("out_rows", C.c_void_p)]
 
 
+LEVEL_COUNT = 5   # DTA_LEVEL_COUNT
+LEVEL_STREAM = 2   # DTA_LEVEL_STREAM
+LEVEL_MAX_SPECIES = 4096   # DTA_LEVEL_MAX_SPECIES
+LEVEL_HEAD, LEVEL_CONIFER, LEVEL_OAK, LEVEL_PLAIN = 0, 1, 2, 3   # DTA_LEVEL_HEAD ..
+
+
+class LevelTables(C.Structure):     # dta_level_tables
+    _fields_ = [("individuals", C.c_longlong), ("records", C.c_longlong), ("species", C.c_int), ("years", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("ind", "year", "sp", "rank", "first", "m", "present", "cls", "lmap", "species_order",
+                                          "record_key")]
+
+
+class LevelConfig(C.Structure):     # dta_level_config
+    _fields_ = [("train", C.c_int), ("other_sampling_ceiling", C.c_longlong), ("evergreen_ceiling", C.c_longlong),
+                ("oaks_sampling_ceiling", C.c_longlong), ("min_loss_weight", C.c_double), ("seed", C.c_ulonglong),
+                ("epoch", C.c_ulonglong)]
+
+
+class LevelOut(C.Structure):        # dta_level_out
+    _fields_ = [("rows", C.c_void_p * LEVEL_COUNT), ("labels", C.c_void_p * LEVEL_COUNT),
+                ("year_keep", C.c_void_p * LEVEL_COUNT), ("capacity", C.c_longlong * LEVEL_COUNT), ("n", C.c_void_p),
+                ("num_classes", C.c_void_p), ("loss_weight", C.c_void_p)]
+
+
 class ReflectanceDesc(C.Structure):     # dta_reflectance_desc
     _fields_ = [(n, C.c_int) for n in ("bands_src", "width_src", "rows", "col0", "cols", "dtype", "tiles", "out_height",
                                        "out_row0")]
@@ -402,6 +426,14 @@ def lib():
         L.dta_pool_batches.restype = C.c_int
         L.dta_pool_batches.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PoolLevel),
                                        C.POINTER(C.c_void_p), vp, vp, vp]
+        L.dta_pool_batches_keep.restype = C.c_int
+        L.dta_pool_batches_keep.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PoolLevel),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, vp]
+        # the five level data sets and their loss weights from one resident table (levels.hip)
+        L.dta_level_workspace_bytes.restype = C.c_size_t
+        L.dta_level_workspace_bytes.argtypes = [C.c_longlong, C.c_longlong, C.c_int, C.c_int]
+        L.dta_level_build.restype = C.c_int
+        L.dta_level_build.argtypes = [C.POINTER(LevelTables), C.POINTER(LevelConfig), C.POINTER(LevelOut), vp, C.c_size_t, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -71,6 +71,7 @@ struct PoolLevel {
   int count, flip;
   long long* out_labels;       // [count] or null
   long long* out_rows;         // [count]
+  const unsigned char* keep;   // [n][Y] or null: 0 masks the (entry, year) as a missing year (dta_pool_batches_keep)
 };
 
 struct PoolArgs {
@@ -112,10 +113,11 @@ template <> struct PoolRaw<bf16_t> {
 };
 
 // The crop of position p and this year, or null: nothing to read, the output is zero (a row outside the pool).
-template <typename T>
+template <typename T, bool KEEP>
 __device__ __forceinline__ const T* pool_crop(const PoolArgs& a, const PoolLevel& v, int p, int y, size_t per) {
   const long long e = pool_entry(v, p);
   if (e < 0) return nullptr;
+  if (KEEP && v.keep && !v.keep[(size_t)e * a.Y + y]) return nullptr;
   const long long row = v.rows[e];
   if (row < 0 || row >= a.N) return nullptr;
   return reinterpret_cast<const T*>(a.pool) + ((size_t)row * a.Y + y) * per;
@@ -132,8 +134,9 @@ __device__ __forceinline__ const T* pool_crop(const PoolArgs& a, const PoolLevel
 constexpr int PB_ITER = 4;
 constexpr int PB_BLOCK = 256 * 4 * PB_ITER;      // floats per workgroup
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_pool_batches(PoolArgs a) {
+// KEEP: the levels may carry a year mask (dta_pool_batches_keep); without it the body is what it was.
+template <typename T, bool KEEP>
+__device__ __forceinline__ void pool_batches_body(const PoolArgs& a) {
   const int net = blockIdx.y, l = net / a.Y, y = net - l * a.Y;
   const PoolLevel& v = a.lv[l];
   if (a.clear_next && blockIdx.x == 0 && threadIdx.x == 0) a.clear_next[net] = 0.f;
@@ -189,6 +192,13 @@ __global__ __launch_bounds__(256) void k_pool_batches(PoolArgs a) {
   long long row[PB_ITER];
 #pragma unroll
   for (int it = 0; it < PB_ITER; ++it) row[it] = v.rows[ent[it]];
+  if (KEEP && v.keep) {      // a masked (entry, year) is a missing year: nothing to read, the output is zero
+    unsigned char kept[PB_ITER];
+#pragma unroll
+    for (int it = 0; it < PB_ITER; ++it) kept[it] = v.keep[(size_t)ent[it] * a.Y + y];
+#pragma unroll
+    for (int it = 0; it < PB_ITER; ++it) ok[it] = ok[it] && kept[it] != 0;
+  }
 #pragma unroll
   for (int it = 0; it < PB_ITER; ++it) {
     ok[it] = ok[it] && row[it] >= 0 && row[it] < a.N;
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(256) void k_pool_batches(PoolArgs a) {
             qq = 0;
             if (++cc == C) {
               cc = 0; ++nn;
-              if (nn < v.count) s = pool_crop<T>(a, v, nn, y, per);
+              if (nn < v.count) s = pool_crop<T, KEEP>(a, v, nn, y, per);
             }
           }
         }
@@ -257,6 +267,13 @@ __global__ __launch_bounds__(256) void k_pool_batches(PoolArgs a) {
   const bool any = __any(hit);
   if (any && (threadIdx.x & 63) == 0) a.flags[net] = 1.f;
 }
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_pool_batches(PoolArgs a) { pool_batches_body<T, false>(a); }
+
+// the same launch for views with a year mask: a masked (entry, year) is gathered as a missing year
+template <typename T>
+__global__ __launch_bounds__(256) void k_pool_masked(PoolArgs a) { pool_batches_body<T, true>(a); }
 
 }  // namespace
 
@@ -300,9 +317,9 @@ int dta_epoch_order(int levels, const long long* n, const int* level_ids, unsign
   return 0;
 }
 
-int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years, int bands, int size, int levels,
-                     const dta_pool_level* lv, float* const* outs, float* flags, float* clear_next, void* stream) {
-  const char* who = "dta_pool_batches";
+static int pool_batches(const char* who, const void* pool, int dtype, long long pool_rows, int years, int bands, int size,
+                        int levels, const dta_pool_level* lv, const unsigned char* const* year_keep, float* const* outs,
+                        float* flags, float* clear_next, void* stream) {
   if (!pool || !lv || !outs || !flags) { dta_set_error("%s: null argument", who); return 1; }
   if (dtype != DTA_F32 && dtype != DTA_BF16) { dta_set_error("%s: dtype=%d: DTA_F32 or DTA_BF16", who, dtype); return 1; }
   if (levels < 1 || levels > DTA_MAX_LEVELS) {
@@ -322,6 +339,7 @@ int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years
   const size_t per = (size_t)bands * size * size;
   if (per > 0x7FFFFFFFull) { dta_set_error("%s: bands=%d x size=%d: a crop of more than 2^31 - 1 floats", who, bands, size); return 1; }
   size_t blocks = 0;
+  bool masked = false;
   for (int l = 0; l < levels; ++l) {
     const dta_pool_level& s = lv[l];
     if (!s.rows || !s.out_rows) { dta_set_error("%s: null rows or out_rows (level %d)", who, l); return 1; }
@@ -337,6 +355,8 @@ int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years
     PoolLevel& d = a.lv[l];
     d.order = s.order; d.rows = s.rows; d.labels = s.labels; d.n = s.n; d.start = s.start; d.count = s.count;
     d.flip = s.flip; d.out_labels = s.out_labels; d.out_rows = s.out_rows;
+    d.keep = year_keep ? year_keep[l] : nullptr;
+    masked = masked || d.keep;
     for (int y = 0; y < years; ++y) {
       float* o = outs[l * years + y];
       if (!o || ((uintptr_t)o & 15)) {
@@ -349,7 +369,7 @@ int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years
     if (b > blocks) blocks = b;
   }
   if (blocks > 0x7FFFFFFFull) { dta_set_error("%s: a batch of more than 2^41 floats", who); return 1; }
-  for (int l = levels; l < DTA_MAX_LEVELS; ++l) a.lv[l] = PoolLevel{nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr};
+  for (int l = levels; l < DTA_MAX_LEVELS; ++l) a.lv[l] = PoolLevel{nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr};
   for (int k = levels * years; k < DTA_MAX_YEARS; ++k) a.out[k] = nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (!clear_next && hipMemsetAsync(flags, 0, sizeof(float) * (size_t)levels * years, st) != hipSuccess) {
@@ -357,10 +377,28 @@ int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years
     return 1;
   }
   const dim3 grid((unsigned)blocks, (unsigned)(levels * years));
-  if (dtype == DTA_F32) hipLaunchKernelGGL(k_pool_batches<float>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_pool_batches<bf16_t>, grid, dim3(256), 0, st, a);
+  if (masked) {
+    if (dtype == DTA_F32) hipLaunchKernelGGL(k_pool_masked<float>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pool_masked<bf16_t>, grid, dim3(256), 0, st, a);
+  } else {
+    if (dtype == DTA_F32) hipLaunchKernelGGL(k_pool_batches<float>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pool_batches<bf16_t>, grid, dim3(256), 0, st, a);
+  }
   DTA_CHECK_LAUNCH("k_pool_batches");
   return 0;
+}
+
+int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years, int bands, int size, int levels,
+                     const dta_pool_level* lv, float* const* outs, float* flags, float* clear_next, void* stream) {
+  return pool_batches("dta_pool_batches", pool, dtype, pool_rows, years, bands, size, levels, lv, nullptr, outs, flags,
+                      clear_next, stream);
+}
+
+int dta_pool_batches_keep(const void* pool, int dtype, long long pool_rows, int years, int bands, int size, int levels,
+                          const dta_pool_level* lv, const unsigned char* const* year_keep, float* const* outs, float* flags,
+                          float* clear_next, void* stream) {
+  return pool_batches("dta_pool_batches_keep", pool, dtype, pool_rows, years, bands, size, levels, lv, year_keep, outs,
+                      flags, clear_next, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,10 @@
                   to nearest even, widened exactly on the way out.
   * `PoolView`    one TreeDataset: int64 rows into the pool and int64 labels, both resident.  `LevelViews` is the list of
                   them `create_datasets` returns; a level is only rows and labels, never a second copy of the crops.  Which
-                  individuals belong to which level stays the caller's pandas work.
+                  individuals belong to which level, in what order and with which labels is levels.py's work
+                  (`levels.create_datasets` returns the `LevelViews`); a view may carry `year_keep`, uint8 [n][Y], where a
+                  level keeps only some of an individual's years (level 3's ceiling counts records): a masked (entry,
+                  year) is gathered as a missing year.
   * the order     `epoch_order_np(n, epoch, seed, level)`: entry i draws
                       key_i = mix(((epoch * n + i) mod 2^64) * 0x9E3779B97F4A7C15 + stream_key(seed, 16 + level)) >> 32
                   (abundance's hash; streams 0 and 1 are abundance's and split's, 16 .. 79 the levels' here) and the entries
@@ -88,14 +91,19 @@ def bf16_round_np(x):
     return r.view(np.float32).reshape(x.shape)
 
 
-def batch_np(crops, rows, train=False):
+def batch_np(crops, rows, train=False, year_keep=None):
     """The definition of a batch: crops [N][Y][C][S][S] (the pool's content), rows the pool rows of the batch in order.
-    Returns one [len(rows)][C][S][S] array per year; train=True: every plane flipped along both axes."""
+    Returns one [len(rows)][C][S][S] array per year; train=True: every plane flipped along both axes.  year_keep: uint8
+    [len(rows)][Y] or None; where it is 0 the crop of that (entry, year) is zeros, as for a missing year."""
     crops = np.asarray(crops)
     rows = np.asarray(rows, np.int64).reshape(-1)
+    if year_keep is not None:
+        year_keep = np.asarray(year_keep).reshape(len(rows), crops.shape[1])
     out = []
     for y in range(crops.shape[1]):
         b = crops[rows, y]
+        if year_keep is not None:
+            b = np.where((year_keep[:, y] != 0)[:, None, None, None], b, np.zeros((), b.dtype))
         out.append(np.ascontiguousarray(b[:, :, ::-1, ::-1] if train else b))
     return out
 
@@ -232,10 +240,11 @@ class CropPool:
         return cls(data, present=present, device=dev, dtype=dtype, **kw)
 
     # ---- views ----------------------------------------------------------------------------------------------------------
-    def view(self, rows, labels=None, train=None, level=0):
+    def view(self, rows, labels=None, train=None, level=0, year_keep=None):
         """One TreeDataset over this pool: `rows` (int64 rows of the pool, in the data set's order) and their labels; train:
-        the data set's own flip setting (PoolView), None to leave it to the caller of loader / batches."""
-        return PoolView(self, rows, labels, train, level)
+        the data set's own flip setting (PoolView), None to leave it to the caller of loader / batches; year_keep: uint8
+        [len(rows)][Y] or None -- 0 masks that year of that entry, which is then gathered as a missing year."""
+        return PoolView(self, rows, labels, train, level, year_keep)
 
     def numpy(self):
         """The pool's content as float32 [N][Y][C][S][S] on the host (a bf16 pool: the stored values, widened)."""
@@ -250,7 +259,7 @@ class PoolView:
     `loader` has the interface of loop.SyntheticTreeDataset.loader, so loop.fit, validate, validate_multistage and
     predict_multistage take a view as it is."""
 
-    def __init__(self, pool, rows, labels=None, train=None, level=0):
+    def __init__(self, pool, rows, labels=None, train=None, level=0, year_keep=None):
         r = np.asarray(_host(rows)).reshape(-1)
         if r.dtype.kind not in "iu" or len(r) < 1:
             raise ValueError("rows must be a non-empty integer array")
@@ -268,6 +277,13 @@ class PoolView:
                 raise ValueError("labels must be one integer per row ({}), got {} {}".format(len(r), y.dtype, y.shape))
             self.labels = labels.to(device=pool.device, dtype=torch.int64).contiguous() if isinstance(labels, torch.Tensor) \
                 else torch.from_numpy(y.astype(np.int64)).to(pool.device)
+        self.year_keep_np = self.year_keep = None
+        if year_keep is not None:
+            k = np.asarray(_host(year_keep))
+            if k.dtype.kind not in "iub" or k.shape != (len(r), pool.n_years):
+                raise ValueError("year_keep must be [{}][{}] of 0 / 1, got {} {}".format(len(r), pool.n_years, k.dtype, k.shape))
+            self.year_keep_np = np.ascontiguousarray(k != 0).astype(np.uint8)
+            self.year_keep = torch.from_numpy(self.year_keep_np).to(pool.device)
 
     def __len__(self):
         return len(self.rows_np)
@@ -287,7 +303,9 @@ class PoolView:
 
     def batch_np(self, positions, train=None):
         """The definition of the batch that brings the entries `positions` of this view (module-level batch_np)."""
-        return batch_np(self.pool.numpy(), self.rows_np[np.asarray(positions, np.int64)], bool(self.train if train is None else train))
+        at = np.asarray(positions, np.int64)
+        return batch_np(self.pool.numpy(), self.rows_np[at], bool(self.train if train is None else train),
+                        None if self.year_keep_np is None else self.year_keep_np[at])
 
     def loader(self, batch_size, shuffle=False, seed=0, drop_last=False, train=None, epoch=0):
         """Yields (individual, {"HSI": [Y tensors], "rows": pool rows}, labels) per batch, one launch each: the view's
@@ -389,6 +407,10 @@ def _steps(views, batch_size, shuffle, seed, train, drop_last, epoch, unset):
     shape = (pool.bands, pool.size, pool.size)
     # two banks of year flags used alternately (dta_year_flags' protocol): a launch sets one and zeroes the other
     banks = torch.zeros(2, nl * Y, dtype=torch.float32, device=dev)
+    # the levels' year masks (PoolView.year_keep), or None: the call without them, as it always was
+    keeps = None
+    if any(v.year_keep is not None for v in views):
+        keeps = (C.c_void_p * nl)(*[None if v.year_keep is None else v.year_keep.data_ptr() for v in views])
     for s in range(steps):
         pos = [step_positions(n, k, B, s) for n, k in zip(sizes, nb)]
         # fresh outputs from torch's allocator: one slab for the crops (every batch 16-byte aligned), one for labels and rows
@@ -412,7 +434,13 @@ def _steps(views, batch_size, shuffle, seed, train, drop_last, epoch, unset):
             entries = np.arange(start, start + count) if orders_np is None else orders_np[l][start:start + count]
             names = [pool.individuals[i] for i in v.rows_np[entries]]
             batch.append((names, {"HSI": xs, "rows": out_rows}, out_labels))
-        _lib.check(L.dta_pool_batches(_lib.ptr(pool.data), code, pool.n, Y, pool.bands, pool.size, nl,
-                                      (_lib.PoolLevel * nl)(*lv), (C.c_void_p * len(outs))(*outs), _lib.ptr(flags),
-                                      _lib.ptr(clear_next), _lib.current_stream_ptr()), "dta_pool_batches")
+        if keeps is None:
+            _lib.check(L.dta_pool_batches(_lib.ptr(pool.data), code, pool.n, Y, pool.bands, pool.size, nl,
+                                          (_lib.PoolLevel * nl)(*lv), (C.c_void_p * len(outs))(*outs), _lib.ptr(flags),
+                                          _lib.ptr(clear_next), _lib.current_stream_ptr()), "dta_pool_batches")
+        else:
+            _lib.check(L.dta_pool_batches_keep(_lib.ptr(pool.data), code, pool.n, Y, pool.bands, pool.size, nl,
+                                               (_lib.PoolLevel * nl)(*lv), keeps, (C.c_void_p * len(outs))(*outs),
+                                               _lib.ptr(flags), _lib.ptr(clear_next), _lib.current_stream_ptr()),
+                       "dta_pool_batches_keep")
         yield batch, flags

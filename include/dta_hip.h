@@ -1078,6 +1078,75 @@ typedef struct {
 } dta_pool_level;
 int dta_pool_batches(const void* pool, int dtype, long long pool_rows, int years, int bands, int size, int levels,
                      const dta_pool_level* lv, float* const* outs, float* flags, float* clear_next, void* stream);
+/* dta_pool_batches_keep: dta_pool_batches with an optional per-level year mask.  year_keep: HOST array of `levels` device
+ * pointers, each unsigned char [n][years] over the VIEW's entries, or NULL for a level without a mask; a NULL year_keep is
+ * dta_pool_batches itself.  Where year_keep[l][e * years + y] is 0 the crop of (entry e, year y) is written as zeros and
+ * does not set the year's flag, exactly as a missing year does.  Everything else as above. */
+int dta_pool_batches_keep(const void* pool, int dtype, long long pool_rows, int years, int bands, int size, int levels,
+                          const dta_pool_level* lv, const unsigned char* const* year_keep, float* const* outs, float* flags,
+                          float* clear_next, void* stream);
+
+/* ---- The five level data sets of the reference's MultiStage.create_datasets (src/models/multi_stage.py:82-219) and the
+ * loss_weight_<level> buffers of its __init__ (:62-79), from one resident integer table.  deeptreeattention_amd/levels.py:
+ * build_np is the definition (it states the rule in full) and the kernels equal it bit for bit.
+ *
+ * All tables are on the device.  Records r = 0 .. records - 1 in frame order; individuals i coded in order of first
+ * appearance.  ind[r], year[r] (0 .. years - 1): the record's individual and year slot; sp[i] (0 .. species - 1): the species
+ * label; rank[i]: the place of i's name among all names sorted as strings; first[i]: i's first record; m[i]: its records;
+ * present[i][y]: 1 when a record of (i, y) exists.  cls[s]: one of DTA_LEVEL_HEAD .. DTA_LEVEL_PLAIN; lmap[l][s]: the level
+ * label of species s in level l, or -1; species_order[s]: the rank of the taxon name.  record_key: int [records], the place
+ * of a record in an explicit shuffle of its species' records, or NULL for the hashed one:
+ *   key_r = mix(((epoch * records + r) mod 2^64) * 0x9E3779B97F4A7C15 + mix(seed * 0x9E3779B97F4A7C15 + DTA_LEVEL_STREAM + 1)) >> 32
+ * Outputs per level l: rows[l], labels[l] (long long [capacity[l]]) and year_keep[l] (unsigned char [capacity[l]][years]):
+ * the kept individuals in data set order -- an entry whose place is at or above capacity[l] is not written; n[l]: how many
+ * the level keeps; num_classes[l]: the level labels present among the kept records; loss_weight (train only): float
+ * [DTA_LEVEL_COUNT][species + 1], the weights of labels 0 .. num_classes[l] - 1 and zeros after them.
+ * workspace: dta_level_workspace_bytes(...) bytes, 16-byte aligned (0: sizes out of range).  At most four launches and one
+ * memset on the stream, no allocation, no host synchronisation.  Integer atomics only (sums and one max, whose result does
+ * not depend on their order): reruns are bit-identical.  About individuals^2 * 6 + records^2 compares.  Every table read is
+ * guarded on the device: a code outside its table belongs to no level.  Refused on the host, before a launch: a null
+ * argument or table, sizes out of range, train other than 0 / 1, a negative ceiling, min_loss_weight outside 0..1, a
+ * capacity outside 0..individuals, a workspace that is too small or misaligned. */
+#define DTA_LEVEL_COUNT 5
+#define DTA_LEVEL_STREAM 2
+#define DTA_LEVEL_MAX_SPECIES 4096
+#define DTA_LEVEL_HEAD 0
+#define DTA_LEVEL_CONIFER 1
+#define DTA_LEVEL_OAK 2
+#define DTA_LEVEL_PLAIN 3
+typedef struct {
+  long long individuals, records;
+  int species, years;
+  const int* ind;
+  const int* year;
+  const int* sp;
+  const int* rank;
+  const int* first;
+  const int* m;
+  const unsigned char* present;
+  const int* cls;
+  const int* lmap;
+  const int* species_order;
+  const int* record_key;
+} dta_level_tables;
+typedef struct {
+  int train;
+  long long other_sampling_ceiling, evergreen_ceiling, oaks_sampling_ceiling;
+  double min_loss_weight;
+  unsigned long long seed, epoch;
+} dta_level_config;
+typedef struct {
+  long long* rows[DTA_LEVEL_COUNT];
+  long long* labels[DTA_LEVEL_COUNT];
+  unsigned char* year_keep[DTA_LEVEL_COUNT];
+  long long capacity[DTA_LEVEL_COUNT];
+  int* n;
+  int* num_classes;
+  float* loss_weight;
+} dta_level_out;
+size_t dta_level_workspace_bytes(long long individuals, long long records, int species, int years);
+int dta_level_build(const dta_level_tables* tables, const dta_level_config* config, const dta_level_out* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
