@@ -19,47 +19,13 @@ import collections
 
 import numpy as np
 
+# the hash is _hash.py's: oracle/prng.py's construction, restated there because the product never imports the oracle
+from ._hash import M64 as _M64, STREAM_ABUNDANCE_DRAW, STREAM_ABUNDANCE_KEEP, draw24, host as _host, shuffle_base
+from ._hash import mix_int as _mix_int, stream_key  # noqa: F401  (their names here, which callers and tests use)
+
 SCALE_BITS = 24
 SCALE = 1 << SCALE_BITS          # a threshold of 2^24 is above every 24-bit draw
 MAX_SPECIES = 256                # DTA_ABUNDANCE_MAX_SPECIES
-
-# the hash: oracle/prng.py's construction (splitmix64's finaliser over a golden-ratio counter), restated because the
-# product never imports the oracle
-_GOLDEN = 0x9E3779B97F4A7C15
-_MUL1 = 0xBF58476D1CE4E5B9
-_MUL2 = 0x94D049BB133111EB
-_M64 = (1 << 64) - 1
-
-
-def _mix_int(z):
-    z = ((z ^ (z >> 30)) * _MUL1) & _M64
-    z = ((z ^ (z >> 27)) * _MUL2) & _M64
-    return z ^ (z >> 31)
-
-
-def stream_key(seed, stream):
-    """The 64-bit key of (seed, stream): mix(seed * 0x9E3779B97F4A7C15 + stream + 1), all modulo 2^64."""
-    return _mix_int(((int(seed) & _M64) * _GOLDEN + int(stream) + 1) & _M64)
-
-
-def _mix(z):
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(_MUL1)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(_MUL2)
-    return z ^ (z >> np.uint64(31))
-
-
-def draw24(seed, stream, counter):
-    """24-bit integers for the uint64 counters `counter` under (seed, stream), all arithmetic modulo 2^64:
-        mix(z)  = z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^ (z >> 31)
-        key     = mix(seed * 0x9E3779B97F4A7C15 + stream + 1)
-        draw    = mix(counter * 0x9E3779B97F4A7C15 + key) >> 40"""
-    with np.errstate(over="ignore"):
-        c = np.asarray(counter, np.uint64)
-        return (_mix(c * np.uint64(_GOLDEN) + np.uint64(stream_key(seed, stream))) >> np.uint64(40)).astype(np.int64)
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
 
 
 def sampling_table(confusion, given="label"):
@@ -135,7 +101,7 @@ def resample_np(label, score, table, iterations, seed=0, first_iteration=0, mask
     """The definition of the resampled counts: int64 [iterations][S + 1].
 
     For iteration t and crown i of N the counter is the 64-bit (first_iteration + t) * N + i (modulo 2^64), and
-        r_keep = draw24(seed, 0, counter),  r_draw = draw24(seed, 1, counter)          (draw24 documents the hash)
+        r_keep = draw24(seed, 0, counter),  r_draw = draw24(seed, 1, counter)          (_hash.py states the hash)
         keep   = not (float32(r_keep) * 2^-24 >= score)        one float32 comparison; a NaN score keeps, score None: all keep
         drawn  = the number of entries of table[label] that are <= r_draw
         final  = label if keep else drawn
@@ -166,10 +132,9 @@ def resample_np(label, score, table, iterations, seed=0, first_iteration=0, mask
     fixed = np.bincount(bins[live & ~inside], minlength=S + 1).astype(np.int64)
     with np.errstate(over="ignore"):
         for it in range(iterations):
-            base = np.uint64(((int(first_iteration) + it) * N) & _M64)
-            counter = base + idx
-            keep = ~((draw24(seed, 0, counter).astype(np.float32) * np.float32(2.0 ** -SCALE_BITS)) >= sc)
-            r = draw24(seed, 1, counter)
+            counter = np.uint64(shuffle_base(int(first_iteration) + it, N)) + idx
+            keep = ~((draw24(seed, STREAM_ABUNDANCE_KEEP, counter).astype(np.float32) * np.float32(2.0 ** -SCALE_BITS)) >= sc)
+            r = draw24(seed, STREAM_ABUNDANCE_DRAW, counter)
             drawn = np.searchsorted(flat, rows * (2 * SCALE + 2) + r, side="right") - rows * S
             out[it] = fixed + np.bincount(np.where(keep, rows, drawn), minlength=S + 1)
     return out

@@ -1,7 +1,7 @@
 // Species abundance with uncertainty (reference src/multinomial.py + sample_multinomial.py: 100 passes of pandas lambdas
 // over every predicted crown; abundance.py: the plain count).  deeptreeattention_amd/abundance.py holds the definition
-// (resample_np / counts_np); these kernels equal it bit for bit: a draw is decided by 64-bit integer arithmetic and ONE
-// float32 comparison, the counts are integer sums.
+// (resample_np / counts_np); these kernels equal it bit for bit: a draw is decided by 64-bit integer arithmetic (the counter
+// hash of hash_dev.h, streams HASH_STREAM_ABUNDANCE_KEEP and _DRAW) and ONE float32 comparison, the counts are integer sums.
 //   k_abundance_resample  every iteration of the resampling in ONE launch: a workgroup owns a slice of crowns and a group of
 //                         AB_G iterations, counts into an LDS histogram [AB_G][species + 1] and stores it whole (zeros
 //                         included) as its slice's partial histogram
@@ -10,6 +10,7 @@
 // No float atomics, no global atomics at all; the table (species^2 thresholds, 160 KB at 200 species) is left to L2.
 #include "../../include/dta_hip.h"
 #include "common.h"
+#include "hash_dev.h"
 
 namespace dta {
 
@@ -17,23 +18,14 @@ constexpr int AB_G = 8;              // iterations per workgroup: a crown's labe
 constexpr int AB_THREADS = 256;
 constexpr int AB_CROWNS = 1024;      // a slice is at least this long (while there are crowns) ...
 constexpr int AB_WORKGROUPS = 2048;  // ... and longer once slices x iteration groups would pass this many workgroups
-constexpr unsigned long long AB_GOLDEN = 0x9E3779B97F4A7C15ull;
 
 struct AbundanceArgs {
   const long long* label; const float* score; const unsigned char* mask; long long n;
   const unsigned* table; int S, iterations;
-  unsigned long long key_keep, key_draw, first;   // the two stream keys (host: ab_key) and first_iteration
+  unsigned long long key_keep, key_draw, first;   // the two stream keys (host: stream_key) and first_iteration
   long long per;                                  // crowns per slice
   unsigned long long* part;                       // [slices][iterations][S + 1]
 };
-
-// splitmix64's finaliser (abundance.py: _mix)
-__host__ __device__ __forceinline__ unsigned long long ab_mix(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-static unsigned long long ab_key(unsigned long long seed, unsigned stream) { return ab_mix(seed * AB_GOLDEN + stream + 1ull); }
 
 __global__ __launch_bounds__(AB_THREADS) void k_abundance_resample(AbundanceArgs a) {
   __shared__ unsigned hist[AB_G * (DTA_ABUNDANCE_MAX_SPECIES + 1)];
@@ -45,7 +37,7 @@ __global__ __launch_bounds__(AB_THREADS) void k_abundance_resample(AbundanceArgs
   const long long i0 = (long long)blockIdx.y * a.per;
   const long long i1 = i0 + a.per < a.n ? i0 + a.per : a.n;
   const unsigned long long N = (unsigned long long)a.n;
-  const unsigned long long step = N * AB_GOLDEN;             // the counter grows by N per iteration
+  const unsigned long long step = N * HASH_GOLDEN;             // the counter grows by N per iteration
   for (long long i = i0 + tid; i < i1; i += AB_THREADS) {
     if (a.mask && a.mask[i] == 0) continue;                  // clipped away by the caller: counted nowhere
     const long long lab = a.label[i];
@@ -57,13 +49,14 @@ __global__ __launch_bounds__(AB_THREADS) void k_abundance_resample(AbundanceArgs
     const int l = (int)lab;
     const float sc = a.score[i];
     const unsigned* row = a.table + (size_t)l * S;
-    // ((first + t0 + t) * N + i) * GOLDEN, formed in 64 bits and modulo 2^64 as the mirror forms it
-    unsigned long long c = ((a.first + (unsigned long long)t0) * N + (unsigned long long)i) * AB_GOLDEN;
+    // ((first + t0 + t) * N + i) * GOLDEN, formed in 64 bits and modulo 2^64 as the mirror forms it; one addition per
+    // iteration instead of hash_dev.h's draw at a counter, which would multiply again for every draw
+    unsigned long long c = ((a.first + (unsigned long long)t0) * N + (unsigned long long)i) * HASH_GOLDEN;
     for (int t = 0; t < nt; ++t, c += step) {
-      const unsigned r_keep = (unsigned)(ab_mix(c + a.key_keep) >> 40);
+      const unsigned r_keep = (unsigned)(mix64(c + a.key_keep) >> 40);
       int bin = l;
       if ((float)r_keep * 0x1p-24f >= sc) {                  // exact in float32; false for a NaN score: it keeps
-        const unsigned r_draw = (unsigned)(ab_mix(c + a.key_draw) >> 40);
+        const unsigned r_draw = (unsigned)(mix64(c + a.key_draw) >> 40);
         // the number of entries <= r_draw of a non-decreasing row: branch-free binary search, S is the same in every lane
         int base = 0, len = S;
         while (len > 1) {
@@ -149,7 +142,8 @@ int dta_abundance_resample(const long long* label, const float* score, const uns
   if (iterations == 0) return 0;                // an empty [0][species + 1]: nothing to write
   AbundanceArgs a;
   a.label = label; a.score = score; a.mask = mask; a.n = n; a.table = table; a.S = species; a.iterations = iterations;
-  a.key_keep = ab_key(seed, 0); a.key_draw = ab_key(seed, 1); a.first = first_iteration;
+  a.key_keep = stream_key(seed, HASH_STREAM_ABUNDANCE_KEEP); a.key_draw = stream_key(seed, HASH_STREAM_ABUNDANCE_DRAW);
+  a.first = first_iteration;
   return ab_run("dta_abundance_resample", p, a, counts, workspace, workspace_bytes, (hipStream_t)stream);
 }
 

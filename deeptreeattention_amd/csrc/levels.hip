@@ -5,17 +5,19 @@
 //                    one integer atomic per workgroup.
 //   k_level_rank     (train only) a lane owns an individual (blockIdx.y = 0) or a record (1) and a (group, key) pair; the
 //                    pairs of its kind stream through LDS in tiles and the lane counts the pairs of ITS group with a smaller
-//                    key, as k_epoch_order does.  Individuals: group = species, key = the rank of the name: pos(i | P) for
-//                    every population P that holds the species.  Records of an OAK species: key = (level-2 shuffle key, r);
+//                    key (hash_dev.h's streamed_count).  Individuals: group = species, key = the rank of the name: pos(i | P) for
+//                    every population P that holds the species.  Records of an OAK species: key = (level-2 shuffle key, r),
+//                    the counter hash's draw32 in stream DTA_LEVEL_STREAM;
 //                    of a CONIFER species: key = r.  A record lane then marks what its count decides: level 2's kept
 //                    individuals, level 3's kept (individual, year) pairs, kept-record counts and first kept records.
 //   k_level_compact  blockIdx.y = level.  A lane owns an individual; the order keys of the level's kept individuals stream
-//                    through LDS and the lane counts the smaller ones: that count is its place in the data set, exactly,
+//                    through LDS (streamed_count again) and the lane counts the smaller ones: that count is its place, exactly,
 //                    because the keys are distinct.  Writes rows, labels and year_keep and adds the class counts.
 //   k_level_weights  per level: the classes present, 1 / count in float64, / max, the floor, rounded to float32.
 // Integer atomics only (sums, one max), whose result does not depend on their order: reruns are bit-identical.
 #include "../../include/dta_hip.h"
 #include "common.h"
+#include "hash_dev.h"
 
 namespace dta {
 
@@ -24,14 +26,7 @@ namespace {
 constexpr int LV_THREADS = 256;
 constexpr int LV_TILE = 1024;      // pairs per LDS tile: 12 KB
 constexpr int LV_LEVELS = DTA_LEVEL_COUNT;
-constexpr unsigned long long LV_GOLDEN = 0x9E3779B97F4A7C15ull;
-constexpr unsigned long long LV_NONE = ~0ull;
-
-__host__ __device__ __forceinline__ unsigned long long lv_mix(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+constexpr unsigned long long LV_NONE = HASH_PAD;      // the key of an entry that takes no part: above every real key
 
 struct LevelArgs {
   int N, R, C, Y;
@@ -107,8 +102,7 @@ __device__ __forceinline__ void lv_pair(const LevelArgs& a, int kind, int j, int
   const int s = lv_species(a, a.ind[j]);
   const int c = lv_class(a, s);
   if (c == DTA_LEVEL_OAK) {
-    const unsigned long long draw = a.okey ? (unsigned long long)(unsigned)a.okey[j]
-                                           : lv_mix((a.base + (unsigned long long)j) * LV_GOLDEN + a.key) >> 32;
+    const unsigned long long draw = a.okey ? (unsigned long long)(unsigned)a.okey[j] : draw32(a.base, a.key, j);
     g = s; k = (draw << 32) | (unsigned)j;
   } else if (c == DTA_LEVEL_CONIFER) {
     g = s; k = (unsigned)j;
@@ -123,19 +117,15 @@ __global__ __launch_bounds__(LV_THREADS) void k_level_rank(LevelArgs a) {
   const int i = blockIdx.x * LV_THREADS + threadIdx.x;
   int g; unsigned long long mine;
   lv_pair(a, kind, i, g, mine);
-  int count = 0;
-  for (int t0 = 0; t0 < n; t0 += LV_TILE) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < LV_TILE; k += LV_THREADS) {
-      int gj; unsigned long long kj;
-      lv_pair(a, kind, t0 + k, gj, kj);
-      tg[k] = gj < 0 ? -2 : gj;                                // (-2: equals no lane's group)
-      tk[k] = kj;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = 0; k < LV_TILE; ++k) count += (tg[k] == g && tk[k] < mine) ? 1 : 0;
-  }
+  const int count = streamed_count<LV_TILE, LV_THREADS>(
+      n,
+      [&](int k, int j) {
+        int gj; unsigned long long kj;
+        lv_pair(a, kind, j, gj, kj);
+        tg[k] = gj < 0 ? -2 : gj;                              // (-2: equals no lane's group)
+        tk[k] = kj;
+      },
+      [&](int k) { return tg[k] == g && tk[k] < mine; });
   if (i >= n || g < 0) return;
   if (kind == 0) { a.pos[i] = count; return; }
   const int who = a.ind[i];                                    // (in range: lv_species said so)
@@ -190,14 +180,8 @@ __global__ __launch_bounds__(LV_THREADS) void k_level_compact(LevelArgs a) {
   const int l = blockIdx.y, n = a.N;
   const int i = blockIdx.x * LV_THREADS + threadIdx.x;
   const unsigned long long mine = lv_order_key(a, l, i);
-  int place = 0;
-  for (int t0 = 0; t0 < n; t0 += LV_TILE) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < LV_TILE; k += LV_THREADS) tile[k] = lv_order_key(a, l, t0 + k);
-    __syncthreads();
-#pragma unroll 8
-    for (int k = 0; k < LV_TILE; ++k) place += tile[k] < mine ? 1 : 0;
-  }
+  const int place = streamed_count<LV_TILE, LV_THREADS>(
+      n, [&](int k, int j) { tile[k] = lv_order_key(a, l, j); }, [&](int k) { return tile[k] < mine; });
   if (mine == LV_NONE) return;
   const int s = a.sp[i];                                       // (in range: lv_order_key said so)
   const int label = a.lmap[l * a.C + s];
@@ -320,7 +304,7 @@ int dta_level_build(const dta_level_tables* t, const dta_level_config* cfg, cons
   a.train = cfg->train;
   a.other_ceiling = cfg->other_sampling_ceiling; a.evergreen_ceiling = cfg->evergreen_ceiling;
   a.oaks_ceiling = cfg->oaks_sampling_ceiling; a.min_loss_weight = cfg->min_loss_weight;
-  a.key = lv_mix(cfg->seed * LV_GOLDEN + (unsigned long long)DTA_LEVEL_STREAM + 1ull);      // abundance.stream_key
+  a.key = stream_key(cfg->seed, DTA_LEVEL_STREAM);
   a.base = cfg->epoch * (unsigned long long)t->records;
   char* w = (char*)workspace;
   a.sums = (int*)(w + sp.sums); a.count_n = (int*)(w + sp.count_n); a.cnt = (int*)(w + sp.cnt);

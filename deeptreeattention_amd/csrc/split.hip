@@ -1,9 +1,9 @@
 // Train/test plot split search (reference src/data.py:108-236: sample_plots run config["iterations"] times, one dask future
 // each, train_test_split keeps the best).  deeptreeattention_amd/split.py holds the definition (order_np / search_np);
-// these kernels equal it bit for bit: the order is a 64-bit integer hash, the scan integer sums and one float64 comparison
-// per species, the choice of the best an integer comparison.
+// these kernels equal it bit for bit: the order is the counter hash's shuffle (hash_dev.h, stream HASH_STREAM_SPLIT), the scan
+// integer sums and one float64 comparison per species, the choice of the best an integer comparison.
 //   k_split_search  ONE WAVEFRONT PER ITERATION, every iteration in one launch.  The wavefront hashes the C candidates into
-//                   64-bit keys (draw32 << 32 | j), sorts them in LDS (bitonic, padded to a power of two), then walks the
+//                   64-bit keys (draw_key), sorts them in LDS (bitonic, padded with HASH_PAD to a power of two), then walks the
 //                   order: lanes over species, 4 per lane (one 16-byte load of a plot's A row, the next plot's row already
 //                   in flight), __ballot for "any species of this plot still wanted", so the walk needs no barrier, and it
 //                   stops as soon as no species is wanted.  The included plots are listed in LDS as they are met; their B and
@@ -14,13 +14,13 @@
 #include <math.h>
 #include "../../include/dta_hip.h"
 #include "common.h"
+#include "hash_dev.h"
 
 namespace dta {
 
 constexpr int SPL_WAVE = 64;
 constexpr int SPL_BEST_THREADS = 256;
 constexpr unsigned SPL_INC = 0x80000000u;   // in the low word of a key once its plot is a test plot (j < 4096 leaves the bit free)
-constexpr unsigned long long SPL_GOLDEN = 0x9E3779B97F4A7C15ull;
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
@@ -34,13 +34,6 @@ struct SplitArgs {
   int* species; long long* train_rows; int* test_plots; unsigned char* membership; unsigned char* taxa;
   double floor[DTA_SPLIT_MAX_SPECIES];
 };
-
-// splitmix64's finaliser (abundance.py: _mix; abundance.hip has the same three lines)
-__host__ __device__ __forceinline__ unsigned long long spl_mix(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __global__ __launch_bounds__(SPL_WAVE) void k_split_search(SplitArgs a) {
   extern __shared__ unsigned long long keys[];        // [n]
@@ -57,7 +50,7 @@ __global__ __launch_bounds__(SPL_WAVE) void k_split_search(SplitArgs a) {
   } else {
     const unsigned long long base = (a.first + it) * (unsigned long long)C;
     for (int k = lane; k < n; k += SPL_WAVE)
-      keys[k] = k < C ? ((spl_mix((base + (unsigned long long)k) * SPL_GOLDEN + a.key) >> 32) << 32) | (unsigned)k : ~0ull;
+      keys[k] = k < C ? draw_key(base, a.key, k) : HASH_PAD;
     __syncthreads();
     // bitonic sort, ascending; the padding keys are above every real key and end behind position C - 1
     for (int size = 2; size <= n; size <<= 1) {
@@ -208,7 +201,7 @@ int dta_split_search(const int* rows, const int* totals, int candidates, int spe
   a.n = SPL_WAVE;
   while (a.n < candidates) a.n <<= 1;
   a.min_train = min_train; a.min_test = min_test;
-  a.key = spl_mix(seed * SPL_GOLDEN + 1ull);      // abundance.stream_key(seed, 0)
+  a.key = stream_key(seed, HASH_STREAM_SPLIT);
   a.first = first_iteration;
   a.species = out_species; a.train_rows = out_train_rows; a.test_plots = out_test_plots; a.membership = membership; a.taxa = taxa;
   hipStream_t st = (hipStream_t)stream;

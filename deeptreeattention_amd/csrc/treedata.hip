@@ -1,10 +1,11 @@
 // The resident training set (reference src/data.py:239-310 `TreeDataset`, five of them over the same individuals in
 // src/models/multi_stage.py:82-219).  deeptreeattention_amd/treedata.py holds the definitions (epoch_order_np / batch_np);
-// these kernels equal them bit for bit: the order is a 64-bit integer hash and a count of smaller keys, a batch a copy.
+// these kernels equal them bit for bit: the order is the counter hash's shuffle (hash_dev.h, streams DTA_EPOCH_ORDER_STREAM +
+// level id), a batch a copy.
 //   k_epoch_order   the shuffled order of every level's view in ONE launch (blockIdx.y = level).  A lane owns entry i and
-//                   its key (draw32 << 32 | i); all keys of the level stream through LDS in tiles (hashed again per tile,
-//                   never read from memory) and the lane counts the keys below its own: that count is the position of i in
-//                   the order, exactly, because the keys are distinct.  n^2 compares, once per epoch.
+//                   its draw_key; all keys of the level stream through LDS in tiles (hash_dev.h's streamed_count) and the
+//                   lane counts the keys below its own: that count is the position of i in the order, exactly, because
+//                   the keys are distinct.  n^2 compares, once per epoch.
 //   k_pool_batches  the float32 batches of every level x year of one step in ONE launch (blockIdx.y = level * years +
 //                   year), with the labels, the pool rows and the level-years' 0/1 flags.  The output of a level-year is
 //                   one flat array; a lane owns pieces of four consecutive floats of it (one 16-byte store each), decomposes a
@@ -15,6 +16,7 @@
 // Pure copies and integer work: no atomics, one writer per output element, reruns are bit-identical.
 #include "../../include/dta_hip.h"
 #include "common.h"
+#include "hash_dev.h"
 
 namespace dta {
 
@@ -22,14 +24,6 @@ namespace {
 
 constexpr int EO_THREADS = 256;
 constexpr int EO_TILE = 1024;      // keys per LDS tile: 8 KB
-constexpr unsigned long long TD_GOLDEN = 0x9E3779B97F4A7C15ull;
-
-// splitmix64's finaliser (abundance.py: _mix; split.hip and abundance.hip have the same three lines)
-__host__ __device__ __forceinline__ unsigned long long td_mix(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 struct EpochOrderArgs {
   int n[DTA_MAX_LEVELS];
@@ -38,28 +32,16 @@ struct EpochOrderArgs {
   int* order[DTA_MAX_LEVELS];
 };
 
-__device__ __forceinline__ unsigned long long td_key(unsigned long long base, unsigned long long key, int i) {
-  return ((td_mix((base + (unsigned long long)i) * TD_GOLDEN + key) >> 32) << 32) | (unsigned)i;
-}
-
 __global__ __launch_bounds__(EO_THREADS) void k_epoch_order(EpochOrderArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned long long tile[EO_TILE];
   const int l = blockIdx.y, n = a.n[l];
   if ((long long)blockIdx.x * EO_THREADS >= n) return;         // (the whole workgroup: the grid is as wide as the longest level)
   const unsigned long long key = a.key[l], base = a.base[l];
   const int i = blockIdx.x * EO_THREADS + threadIdx.x;
-  const unsigned long long mine = i < n ? td_key(base, key, i) : 0ull;
-  int rank = 0;
-  for (int t0 = 0; t0 < n; t0 += EO_TILE) {
-    __syncthreads();
-    for (int k = threadIdx.x; k < EO_TILE; k += EO_THREADS) {
-      const int j = t0 + k;
-      tile[k] = j < n ? td_key(base, key, j) : ~0ull;          // the padding is above every key (a key's low word is < n)
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = 0; k < EO_TILE; ++k) rank += tile[k] < mine ? 1 : 0;      // every lane reads the same word: a broadcast
-  }
+  const unsigned long long mine = i < n ? draw_key(base, key, i) : 0ull;      // (0: no key is below it)
+  const int rank = streamed_count<EO_TILE, EO_THREADS>(
+      n, [&](int k, int j) { tile[k] = j < n ? draw_key(base, key, j) : HASH_PAD; },      // hashed again, never read from memory
+      [&](int k) { return tile[k] < mine; });
   if (i < n && rank < n) a.order[l][rank] = i;
 }
 
@@ -305,7 +287,7 @@ int dta_epoch_order(int levels, const long long* n, const int* level_ids, unsign
       return 1;
     }
     a.n[l] = (int)n[l];
-    a.key[l] = td_mix(seed * TD_GOLDEN + (unsigned long long)(DTA_EPOCH_ORDER_STREAM + id) + 1ull);   // abundance.stream_key
+    a.key[l] = stream_key(seed, (unsigned long long)(DTA_EPOCH_ORDER_STREAM + id));
     a.base[l] = epoch * (unsigned long long)n[l];
     a.order[l] = orders[l];
     if (n[l] > longest) longest = n[l];

@@ -17,10 +17,10 @@
                     individual: no effect.)
                L2   neither HEAD nor CONIFER: every non-OAK individual; per OAK species the records in shuffled order, the
                     first k2 = (non-OAK records) // 5 of them name the kept individuals (one named twice is kept once, with
-                    all its records); by first.  The shuffle: record r draws
-                        key_r = mix(((epoch * R + r) mod 2^64) * 0x9E3779B97F4A7C15 + stream_key(seed, 2)) >> 32
-                    and a species' records sort ascending by (key_r, r) -- or `orders` hands in explicit orders (the
-                    fixture: the reference's own `sample(frac=1)` results).
+                    all its records); by first.  The shuffle: record r draws key_r = draw32 at the counter epoch * R + r
+                    of stream 2 (_hash.py: the counter hash and the streams in use) and a species' records sort ascending
+                    by (key_r, r) -- or `orders` hands in explicit orders (the fixture: the reference's own
+                    `sample(frac=1)` results).
                L3   CONIFER: per species the first evergreen_ceiling RECORDS in frame order; an individual is kept when a
                     record of it is, with year_keep[i][y] = 1 only where a kept record of (i, y) exists; species ascending by
                     species_order, within a species by the first kept record.
@@ -42,7 +42,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .abundance import _GOLDEN, _M64, _host, _mix, stream_key
+from ._hash import M64 as _M64, draw32, host as _host, shuffle_base
 from .hierarchy import Hierarchy
 from .split import _codes
 from .treedata import LevelViews, PoolView
@@ -277,11 +277,8 @@ def record_keys_np(table, rules, orders):
 
 
 def hashed_keys_np(n_records, epoch=0, seed=0):
-    """key_r = mix(((epoch * R + r) mod 2^64) * 0x9E3779B97F4A7C15 + stream_key(seed, 2)) >> 32, uint64 [R]."""
-    base = np.uint64(((int(epoch) & _M64) * int(n_records)) & _M64)
-    r = np.arange(int(n_records), dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        return _mix((base + r) * np.uint64(_GOLDEN) + np.uint64(stream_key(seed, STREAM))) >> np.uint64(32)
+    """key_r, uint64 [R]: _hash.py's draw32 of the R records in stream STREAM, starting at the counter epoch * R."""
+    return draw32(seed, STREAM, shuffle_base(epoch, n_records), n_records)
 
 
 def _check(table, rules):

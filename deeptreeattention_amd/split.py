@@ -24,8 +24,8 @@ in T.  min_train and min_test are at least 1: with 0 the reference drops a speci
 its isin() lines, which T would keep.
 
 The reference shuffles with NumPy's global generator; a device cannot follow that stream, so the order is this package's
-(abundance's hash): candidate j of iteration t draws  mix((t * C + j) * GOLDEN + stream_key(seed, 0)) >> 32  and the
-candidates are sorted ascending by (draw, j).  An explicit `orders` array replaces the hash in the definition and on the
+(_hash.py's counter hash and shuffle): candidate j of iteration t draws  draw32  at the counter t * C + j of stream 0 and
+the candidates are sorted ascending by (draw, j).  An explicit `orders` array replaces the hash in the definition and on the
 device alike; with the reference's own shuffles it reproduces the reference exactly
 (tests/golden/split/split_reference.npz).
 
@@ -36,7 +36,7 @@ import collections
 
 import numpy as np
 
-from .abundance import _GOLDEN, _M64, _host, _mix, stream_key
+from ._hash import M64 as _M64, STREAM_SPLIT, draw32, host as _host, order_of, shuffle_base
 
 MAX_SPECIES = 256          # DTA_SPLIT_MAX_SPECIES
 MAX_CANDIDATES = 4096      # DTA_SPLIT_MAX_CANDIDATES
@@ -63,21 +63,16 @@ def _codes(values):
 
 
 def order_np(candidates, iteration, seed=0):
-    """The order of the candidates in the 64-bit iteration number(s) `iteration`: int32 [C] (or [n][C] for an array of n).
-        draw32 = mix(((iteration * C + j) mod 2^64) * 0x9E3779B97F4A7C15 + stream_key(seed, 0)) >> 32     (abundance.draw24's mix)
-    and the candidates sorted ascending by (draw32, j)."""
+    """The order of the candidates in the 64-bit iteration number(s) `iteration`: int32 [C] (or [n][C] for an array of n):
+    _hash.py's shuffle of C in stream STREAM_SPLIT, iteration t starting at the counter t * C."""
     C = int(candidates)
     if not 1 <= C <= MAX_CANDIDATES:
         raise ValueError("candidates must be 1..{}".format(MAX_CANDIDATES))
+    if not isinstance(iteration, (list, tuple, np.ndarray)):
+        return order_of(draw32(seed, STREAM_SPLIT, shuffle_base(iteration, C), C))
     # (Python integers all the way: NumPy would turn a list that holds numbers of 2^63 and more into float64)
-    scalar = not isinstance(iteration, (list, tuple, np.ndarray))
-    its = [iteration] if scalar else np.asarray(iteration).reshape(-1).tolist() if isinstance(iteration, np.ndarray) else list(iteration)
-    base = np.array([((int(t) & _M64) * C) & _M64 for t in its], np.uint64)
-    j = np.arange(C, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        draw = _mix((base[:, None] + j) * np.uint64(_GOLDEN) + np.uint64(stream_key(seed, 0))) >> np.uint64(32)
-        order = np.argsort((draw << np.uint64(32)) | j, axis=1, kind="stable").astype(np.int32)
-    return order[0] if scalar else order
+    its = np.asarray(iteration).reshape(-1).tolist() if isinstance(iteration, np.ndarray) else list(iteration)
+    return order_of(draw32(seed, STREAM_SPLIT, [shuffle_base(t, C) for t in its], C))
 
 
 def check_orders(orders, iterations, candidates):

@@ -11,9 +11,8 @@
                   (`levels.create_datasets` returns the `LevelViews`); a view may carry `year_keep`, uint8 [n][Y], where a
                   level keeps only some of an individual's years (level 3's ceiling counts records): a masked (entry,
                   year) is gathered as a missing year.
-  * the order     `epoch_order_np(n, epoch, seed, level)`: entry i draws
-                      key_i = mix(((epoch * n + i) mod 2^64) * 0x9E3779B97F4A7C15 + stream_key(seed, 16 + level)) >> 32
-                  (abundance's hash; streams 0 and 1 are abundance's and split's, 16 .. 79 the levels' here) and the entries
+  * the order     `epoch_order_np(n, epoch, seed, level)`: entry i draws key_i = draw32 at the counter epoch * n + i of
+                  stream 16 + level (_hash.py: the counter hash, the shuffle and the streams in use) and the entries
                   are sorted ascending by (key_i, i).  A pure function of (seed, epoch, level): an epoch can be resumed, the
                   ranks of a data-parallel run agree on it without talking, and the host names the individuals of a batch
                   without asking the device.  dta_epoch_order computes every level's order in one launch, by counting the
@@ -35,27 +34,23 @@ import numpy as np
 import torch
 
 from . import _lib
-from .abundance import _GOLDEN, _M64, _host, _mix, stream_key
+from ._hash import M64 as _M64, draw32, host as _host, order_of, shuffle_base
 from .split import _codes
 
 MAX_N = _lib.EPOCH_ORDER_MAX_N               # entries of one view that dta_epoch_order sorts
-ORDER_STREAM = _lib.EPOCH_ORDER_STREAM       # stream_key(seed, ORDER_STREAM + level): 0 and 1 are abundance's and split's
+ORDER_STREAM = _lib.EPOCH_ORDER_STREAM       # stream ORDER_STREAM + level (_hash.py lists the streams in use)
 MAX_LEVEL_ID = _lib.EPOCH_ORDER_MAX_LEVEL_ID
 
 
 def epoch_order_np(n, epoch=0, seed=0, level=0):
-    """The order of a view of n entries in `epoch`: int32 [n], the entries sorted ascending by (key_i, i) with
-        key_i = mix(((epoch * n + i) mod 2^64) * 0x9E3779B97F4A7C15 + stream_key(seed, 16 + level)) >> 32."""
+    """The order of a view of n entries in `epoch`: int32 [n], _hash.py's shuffle of n in stream ORDER_STREAM + level,
+    starting at the counter epoch * n."""
     n, level = int(n), int(level)
     if n < 1:
         raise ValueError("n must be at least 1, got {}".format(n))
     if not 0 <= level < MAX_LEVEL_ID:
         raise ValueError("level must be 0..{}, got {}".format(MAX_LEVEL_ID - 1, level))
-    base = np.uint64(((int(epoch) & _M64) * n) & _M64)
-    i = np.arange(n, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        key = _mix((base + i) * np.uint64(_GOLDEN) + np.uint64(stream_key(seed, ORDER_STREAM + level))) >> np.uint64(32)
-        return np.argsort((key << np.uint64(32)) | i, kind="stable").astype(np.int32)
+    return order_of(draw32(seed, ORDER_STREAM + level, shuffle_base(epoch, n), n))
 
 
 def plan(sizes, batch_size, drop_last=False):

@@ -155,7 +155,9 @@ def test_flip_defaults_a_loader_does_not_flip_and_training_batches_do():
 
 def test_epoch_order_equals_the_definition_several_levels_in_one_launch():
     from deeptreeattention_amd import treedata as T
-    for sizes, ids in (((1, 63, 64, 65, 1000), None), ((4097, 20000, 64), (7, 0, 63))):
+    # (the third launch: sizes either side of the workgroup and of the LDS tile, so whole workgroups of the shorter levels
+    # leave before the first barrier while their neighbours in the grid stay)
+    for sizes, ids in (((1, 63, 64, 65, 1000), None), ((4097, 20000, 64), (7, 0, 63)), ((255, 256, 257, 1023, 1024, 1025), None)):
         got = T.epoch_order(sizes, epoch=2 ** 40 + 3, seed=11, levels=ids, device=dev())
         for k, n in enumerate(sizes):
             want = T.epoch_order_np(n, 2 ** 40 + 3, 11, k if ids is None else ids[k])

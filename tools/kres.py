@@ -14,5 +14,5 @@ for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
     if filt and not any(k in dn for k in filt):
         continue
     g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
-    print(dn[:110], "| VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "spill", g("VGPRs Spill") if "VGPRs Spill" in b else g("VGPR Spill"), "scratch", g(r"ScratchSize \[bytes/lane\]"),
+    print(dn[:110], "| VGPR", g("VGPRs"), "SGPR", g("SGPRs"), "AGPR", g("AGPRs"), "spill", g("VGPRs Spill") if "VGPRs Spill" in b else g("VGPR Spill"), "scratch", g(r"ScratchSize \[bytes/lane\]"),
           "occ", g(r"Occupancy \[waves/SIMD\]"), "LDS", g(r"LDS Size \[bytes/block\]"))
