@@ -92,6 +92,9 @@ class HierarchyTable(C.Structure):  # dta_hierarchy
 
 ADAM_MAX_SEGMENTS = 16   # DTA_ADAM_MAX_SEGMENTS
 ABUNDANCE_MAX_SPECIES = 256   # DTA_ABUNDANCE_MAX_SPECIES
+ABUNDANCE_SUMMARY_MAX_ITERATIONS = 256   # DTA_ABUNDANCE_SUMMARY_MAX_ITERATIONS
+ABUNDANCE_SUMMARY_MAX_QUANTILES = 16   # DTA_ABUNDANCE_SUMMARY_MAX_QUANTILES
+CELLS_GEOINDEX, CELLS_CENTRE = 0, 1   # DTA_CELLS_*
 CROWN_WAVE_CELLS = 1024   # DTA_CROWN_WAVE_CELLS
 ELEM_F32, ELEM_BF16, ELEM_F16 = 0, 1, 2   # DTA_ELEM_*
 RGB_CROPS_MAX_GROUPS = 1024   # DTA_RGB_CROPS_MAX_GROUPS
@@ -389,6 +392,18 @@ def lib():
                                              vp, C.c_size_t, vp]
         L.dta_abundance_counts.restype = C.c_int
         L.dta_abundance_counts.argtypes = [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_size_t, vp]
+        # abundance per tile and map cell: the cell of a crown, grouped counts and resampling, the summary (abundance_grid.hip)
+        L.dta_abundance_cells.restype = C.c_int
+        L.dta_abundance_cells.argtypes = [vp, C.c_longlong, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, vp, vp]
+        L.dta_abundance_grouped_workspace_bytes.restype = C.c_size_t
+        L.dta_abundance_grouped_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_longlong]
+        L.dta_abundance_resample_grouped.restype = C.c_int
+        L.dta_abundance_resample_grouped.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, C.c_int, C.c_int,
+                                                     C.c_ulonglong, C.c_ulonglong, vp, vp, C.c_size_t, vp]
+        L.dta_abundance_counts_grouped.restype = C.c_int
+        L.dta_abundance_counts_grouped.argtypes = [vp, vp, vp, vp, C.c_longlong, C.c_longlong, C.c_int, vp, vp, C.c_size_t, vp]
+        L.dta_abundance_summary.restype = C.c_int
+        L.dta_abundance_summary.argtypes = [vp, C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, vp, vp, vp]
         # crown height filter: CHM quantile per box and the keep rules (canopy.hip)
         L.dta_crown_height.restype = C.c_int
         L.dta_crown_height.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, C.c_float, C.c_float, vp, C.POINTER(HeightRule),

@@ -9,66 +9,25 @@
 //                         pass instead of global atomics, so nothing has to be cleared and nothing is left behind
 // No float atomics, no global atomics at all; the table (species^2 thresholds, 160 KB at 200 species) is left to L2.
 #include "../../include/dta_hip.h"
-#include "common.h"
-#include "hash_dev.h"
+#include "abundance_dev.h"
 
 namespace dta {
 
-constexpr int AB_G = 8;              // iterations per workgroup: a crown's label, score and mask byte are read once for them
-constexpr int AB_THREADS = 256;
-constexpr int AB_CROWNS = 1024;      // a slice is at least this long (while there are crowns) ...
-constexpr int AB_WORKGROUPS = 2048;  // ... and longer once slices x iteration groups would pass this many workgroups
-
-struct AbundanceArgs {
-  const long long* label; const float* score; const unsigned char* mask; long long n;
-  const unsigned* table; int S, iterations;
-  unsigned long long key_keep, key_draw, first;   // the two stream keys (host: stream_key) and first_iteration
-  long long per;                                  // crowns per slice
-  unsigned long long* part;                       // [slices][iterations][S + 1]
-};
-
+// (the constants, AbundanceArgs, the plan and the body of a crown's draws are abundance_dev.h's: abundance_grid.hip counts
+// the same draws per cell)
 __global__ __launch_bounds__(AB_THREADS) void k_abundance_resample(AbundanceArgs a) {
   __shared__ unsigned hist[AB_G * (DTA_ABUNDANCE_MAX_SPECIES + 1)];
-  const int S = a.S, bins = S + 1, tid = threadIdx.x;
+  const int bins = a.S + 1, tid = threadIdx.x;
   const int t0 = blockIdx.x * AB_G;
   const int nt = a.iterations - t0 < AB_G ? a.iterations - t0 : AB_G;
   for (int e = tid; e < nt * bins; e += AB_THREADS) hist[e] = 0u;
   __syncthreads();
   const long long i0 = (long long)blockIdx.y * a.per;
   const long long i1 = i0 + a.per < a.n ? i0 + a.per : a.n;
-  const unsigned long long N = (unsigned long long)a.n;
-  const unsigned long long step = N * HASH_GOLDEN;             // the counter grows by N per iteration
+  const AbundanceDraw d = ab_draw(a, t0, nt);
   for (long long i = i0 + tid; i < i1; i += AB_THREADS) {
     if (a.mask && a.mask[i] == 0) continue;                  // clipped away by the caller: counted nowhere
-    const long long lab = a.label[i];
-    if (lab < 0 || lab >= S || !a.score) {                   // DEAD / unresolved: bin S; no scores: every crown keeps
-      const int bin = (lab < 0 || lab >= S) ? S : (int)lab;
-      for (int t = 0; t < nt; ++t) atomicAdd(&hist[t * bins + bin], 1u);
-      continue;
-    }
-    const int l = (int)lab;
-    const float sc = a.score[i];
-    const unsigned* row = a.table + (size_t)l * S;
-    // ((first + t0 + t) * N + i) * GOLDEN, formed in 64 bits and modulo 2^64 as the mirror forms it; one addition per
-    // iteration instead of hash_dev.h's draw at a counter, which would multiply again for every draw
-    unsigned long long c = ((a.first + (unsigned long long)t0) * N + (unsigned long long)i) * HASH_GOLDEN;
-    for (int t = 0; t < nt; ++t, c += step) {
-      const unsigned r_keep = (unsigned)(mix64(c + a.key_keep) >> 40);
-      int bin = l;
-      if ((float)r_keep * 0x1p-24f >= sc) {                  // exact in float32; false for a NaN score: it keeps
-        const unsigned r_draw = (unsigned)(mix64(c + a.key_draw) >> 40);
-        // the number of entries <= r_draw of a non-decreasing row: branch-free binary search, S is the same in every lane
-        int base = 0, len = S;
-        while (len > 1) {
-          const int half = len >> 1;
-          base = row[base + half - 1] <= r_draw ? base + half : base;
-          len -= half;
-        }
-        bin = base + (row[base] <= r_draw ? 1 : 0);          // < S: every row ends at 2^24, above every draw
-        bin = bin < S ? bin : S - 1;                         // (a table that breaks that rule cannot leave the histogram)
-      }
-      atomicAdd(&hist[t * bins + bin], 1u);
-    }
+    ab_crown(d, i, a.label[i], a.score ? a.score + i : nullptr, [&](int t, int bin) { atomicAdd(&hist[t * bins + bin], 1u); });
   }
   __syncthreads();
   unsigned long long* dst = a.part + ((size_t)blockIdx.y * a.iterations + t0) * bins;
@@ -82,28 +41,6 @@ __global__ __launch_bounds__(AB_THREADS) void k_abundance_sum(const unsigned lon
   unsigned long long s = 0;
   for (int k = 0; k < slices; ++k) s += part[(size_t)k * total + e];
   counts[e] = (long long)s;
-}
-
-struct AbundancePlan { int groups, slices; long long per; size_t bytes; };
-
-// 0 on success; the plan depends on (n, species, iterations) alone, so dta_abundance_workspace_bytes and the calls agree
-static int ab_plan(const char* who, long long n, int species, int iterations, AbundancePlan* p) {
-  if (n < 1) { dta_set_error("%s: bad shape: n=%lld", who, n); return 1; }
-  if (species < 1 || species > DTA_ABUNDANCE_MAX_SPECIES) {
-    dta_set_error("%s: species=%d: 1..%d (DTA_ABUNDANCE_MAX_SPECIES)", who, species, DTA_ABUNDANCE_MAX_SPECIES);
-    return 1;
-  }
-  if (iterations < 0) { dta_set_error("%s: iterations=%d is negative", who, iterations); return 1; }
-  p->groups = (iterations + AB_G - 1) / AB_G;
-  const long long cap = p->groups >= AB_WORKGROUPS ? 1 : AB_WORKGROUPS / (p->groups > 0 ? p->groups : 1);
-  long long slices = (n + AB_CROWNS - 1) / AB_CROWNS;
-  slices = slices > cap ? cap : slices;
-  p->slices = (int)slices;
-  p->per = (n + slices - 1) / slices;
-  if (p->per > 0xFFFFFFFFll) { dta_set_error("%s: n=%lld: too many crowns per workgroup for 32-bit bins", who, n); return 1; }
-  if ((long long)iterations * (species + 1) > 0x7FFFFFFFll * AB_THREADS) { dta_set_error("%s: iterations=%d: too many for one launch", who, iterations); return 1; }
-  p->bytes = sizeof(unsigned long long) * (size_t)slices * (size_t)(iterations > 0 ? iterations : 1) * (size_t)(species + 1);
-  return 0;
 }
 
 static int ab_run(const char* who, const AbundancePlan& p, AbundanceArgs a, long long* counts, void* workspace,

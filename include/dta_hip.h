@@ -831,6 +831,69 @@ int dta_abundance_resample(const long long* label, const float* score, const uns
 int dta_abundance_counts(const long long* label, const unsigned char* mask, long long n, int species, long long* counts,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Abundance per tile and map cell (the reference counts a site tile by tile: src/multinomial.py:run resamples one
+ * tile, abundance.py:read_shp counts one, src/neon_paths.py:bounds_to_geoindex says which 1 km tile a crown belongs to).
+ * deeptreeattention_amd/abundance.py: cells_np, the group= forms of counts_np / resample_np and summary_np are the
+ * definitions and the kernels equal them bit for bit.
+ *
+ * dta_abundance_cells: cell[i] = row * cols + col of crown box i, rows growing with northing, or -1 outside the
+ * cols x rows grid.  boxes: double [n][4] (xmin, ymin, xmax, ymax) on the device; origin: double [2] on the HOST.  All
+ * arithmetic in double, every operation rounded on its own (no FMA).  Per axis, with (lo, hi) the box's two coordinates:
+ *   DTA_CELLS_GEOINDEX  e = trunc((lo + hi) / 2), toward zero as Python's int();  k = floor_div(e - origin, size) in
+ *                       integers: the reference's rule with origin 0 and size 1000.  size and origin must be integers
+ *                       (size <= 2^31-1, |origin| < 2^53); a centre that is not finite or not below 2^53 gives -1
+ *   DTA_CELLS_CENTRE    k = floor(((lo + hi) * 0.5 - origin) / size), any finite origin and positive size
+ * One launch.  Refused before it: a null boxes / origin / cell, n < 1, cols or rows < 1, another rule, a size that is not
+ * positive and finite, an origin that is not finite, a non-integer size or origin under DTA_CELLS_GEOINDEX. */
+#define DTA_CELLS_GEOINDEX 0
+#define DTA_CELLS_CENTRE 1
+int dta_abundance_cells(const double* boxes, long long n, int rule, const double* origin, double size, int cols, int rows,
+                        long long* cell, void* stream);
+
+/* dta_abundance_resample_grouped: dta_abundance_resample per cell in one call.  counts: int64 [iterations][groups]
+ * [species + 1]; plane g is dta_abundance_resample with mask[i] && group[i] == g on the same n, seed and first_iteration:
+ * the counter of a draw is the crown's index in the WHOLE input, so a crown draws the same species whichever cell it is
+ * counted in.  A crown whose group is outside [0, groups) is counted nowhere.
+ * The caller orders the crowns by cell: group_sorted int64 [n], the groups ascending, and order int64 [n], the crown at
+ * each sorted position (torch.sort(group, stable=True) gives both; the sums are integers, so the order among equal groups
+ * changes nothing).  An order entry outside [0, n) is counted nowhere.  Nothing is read back from the device: a workgroup
+ * owns a FIXED slice of sorted positions (the slices of dta_abundance_resample) and 8 iterations, whatever the cells'
+ * sizes, and walks the runs of equal cell inside its slice; a crown is read once per 8 iterations.
+ * counts is OVERWRITTEN in full (cleared by a memset on `stream` in front of the kernels; empty cells are zeros; the
+ * caller clears nothing); a cell may lie in several slices, so its partial counts are added with 64-bit integer atomics:
+ * any order gives the same sums, reruns are bit-identical.  No float atomics.  workspace:
+ * dta_abundance_grouped_workspace_bytes(n, species, iterations, groups) bytes (0 and dta_last_error() for a bad shape),
+ * 8-byte aligned, written in full before it is read: nothing in it survives a call.  1 <= groups <= 2^31-2; the other
+ * bounds are dta_abundance_resample's.  Three stream operations: the memset, a gather of the crowns into cell order, the
+ * resampling. */
+size_t dta_abundance_grouped_workspace_bytes(long long n, int species, int iterations, long long groups);
+int dta_abundance_resample_grouped(const long long* label, const float* score, const unsigned char* mask,
+                                   const long long* group_sorted, const long long* order, long long n, long long groups,
+                                   const unsigned int* table, int species, int iterations, unsigned long long seed,
+                                   unsigned long long first_iteration, long long* counts, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+/* The plain count per cell: counts int64 [groups][species + 1], overwritten in full; the workspace of
+ * dta_abundance_grouped_workspace_bytes(n, species, 1, groups). */
+int dta_abundance_counts_grouped(const long long* label, const unsigned char* mask, const long long* group_sorted,
+                                 const long long* order, long long n, long long groups, int species, long long* counts,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* dta_abundance_summary: mean and quantiles over the iterations of a resampled table, grouped or not.  table: int64
+ * [iterations][entries] on the device; mean: double [entries]; out_quantiles: double [quantiles][entries].  Per entry:
+ *   mean = (double)(integer sum over the iterations) / (double)iterations
+ *   quantile j: a, b = the lower[j]-th and min(lower[j] + 1, iterations - 1)-th smallest value (0-based), d = b - a,
+ *               frac[j] >= 0.5 ? b - d * (1 - frac[j]) : a + d * frac[j]      every operation rounded on its own (no FMA)
+ * lower / frac: HOST arrays: floor(q * (iterations - 1)) and the remainder, formed by the caller in double (NumPy's linear
+ * rule; abundance.summary_np is the definition).  One launch: a workgroup stages iterations x 64 adjacent entries in LDS
+ * and one lane sorts one column, which bounds iterations by DTA_ABUNDANCE_SUMMARY_MAX_ITERATIONS (128 KB of the 160 KB).
+ * Refused before the launch: a null table / mean (lower / frac / out_quantiles with quantiles > 0), iterations outside
+ * 1..DTA_ABUNDANCE_SUMMARY_MAX_ITERATIONS, entries < 1, quantiles outside 0..DTA_ABUNDANCE_SUMMARY_MAX_QUANTILES, a lower
+ * outside [0, iterations) or a frac outside [0, 1). */
+#define DTA_ABUNDANCE_SUMMARY_MAX_ITERATIONS 256
+#define DTA_ABUNDANCE_SUMMARY_MAX_QUANTILES 16
+int dta_abundance_summary(const long long* table, int iterations, long long entries, const int* lower, const double* frac,
+                          int quantiles, double* mean, double* out_quantiles, void* stream);
+
 /* ---- Crown height filter: the canopy-height statistic of every crown box of a resident CHM raster, and the reference's keep
  * rules on it (src/CHM.py:9-14 non_zero_99_quantile, run per crown through rasterstats.zonal_stats; :58-95 height_rules;
  * src/predict.py:35-42 find_crowns: CHM_height > 3).  chm: float32 [height][width] on the device.  boxes: int32 [n][4] =
