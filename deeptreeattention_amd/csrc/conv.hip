@@ -489,6 +489,9 @@ static int launch_conv_t(ConvArgs a, int G, hipStream_t st) {
   constexpr int MWG = 4 * MT * 32, N = NT * 32;
   int nwg;
   conv_geometry(a.HW, MWG, a.B, &a.ppw, &a.spp, &nwg);
+  // fewer patches than one workgroup's rows hold: the kernel stages and reads only the B tiles that exist, so the LDS
+  // is sized for those (a 2x2 map has 128 tile slots per 512-row workgroup: 131 KB of fp32 tiles for a batch of one)
+  if (a.B < a.ppw) a.ppw = a.B;
   size_t lds = (size_t)MWG * 8 + (size_t)5 * N * 4 + ((size_t)a.ppw * a.Q * 16 + (size_t)9 * N * 16) * sizeof(T);
   if (lds > 160 * 1024) { dta_set_error("conv3x3: LDS need %zu B exceeds 160 KiB (H=%d W=%d)", lds, a.H, a.W); return 1; }
   static DevOnce attr_once;      // (function attributes are per device)

@@ -738,13 +738,26 @@ __device__ long long g_wticks[64];
 extern "C" int dta_debug_wticks(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wticks), sizeof(long long) * 64); }
 #define WTICK_DECL long long wt_[5] = {0, 0, 0, 0, 0}, wacc_[4] = {0, 0, 0, 0}; const long long wt0_ = clock64();
 #define WTICK(i) wt_[i] = clock64(); if (i == 4) { wacc_[0] += wt_[1] - wt_[0]; wacc_[1] += wt_[2] - wt_[1]; wacc_[2] += wt_[3] - wt_[2]; wacc_[3] += wt_[4] - wt_[3]; }
-#define WTICK_DUMP if (blockIdx.x == 17 && lane == 0 && a.N == 64 && a.NCx > 8) { long long* o_ = g_wticks + wave * 8; \
+// the instrumented workgroup: number 17 of the first conv's job (-DDTA_TICKS_JOB=0, the default), of the pair launch's
+// second-conv job (1) or of its third-conv job (2)
+#ifndef DTA_TICKS_JOB
+#define DTA_TICKS_JOB 0
+#endif
+#define WTICK_GATE (bx == 17 && (DTA_TICKS_JOB == 0 ? (a.N == 64 && a.NCx > 8) : DTA_TICKS_JOB == 1 ? (a.N == 64 && a.NCx <= 8) : a.N == 128))
+#define WTICK_DUMP if (WTICK_GATE && lane == 0) { long long* o_ = g_wticks + wave * 8; \
     o_[0] = wacc_[0]; o_[1] = wacc_[1]; o_[2] = wacc_[2]; o_[3] = clock64() - wt0_; o_[4] = niter; o_[5] = wacc_[3]; }
 #else
 #define WTICK_DECL
 #define WTICK(i)
 #define WTICK_DUMP
 #endif
+// taps per pass of the slab epilogue's LDS image (32 KiB each; cycle stamps: profiles/wgrad_epilogue_phase_stamps.txt)
+#ifndef DTA_WGRAD_EPI_T
+#define DTA_WGRAD_EPI_T 3
+#endif
+constexpr int WGRAD_EPI_T = DTA_WGRAD_EPI_T;
+constexpr size_t WGRAD_EPI_LDS = (size_t)WGRAD_EPI_T * 32 * 1024;
+static_assert(WGRAD_EPI_T >= 2 && WGRAD_EPI_LDS <= 160 * 1024, "the epilogue's image must fit the LDS and cover the first epilogue's 48 KiB");
 // The workgroup program; bx = index of this workgroup among the job's workgroups (a launch may carry two jobs: below).
 template <int CT, int NTT, bool BIGW, bool STACK = false, bool D2 = false>
 __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx, unsigned char* smem) {
@@ -815,6 +828,10 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx
   const int ppi = STACK ? a.ppi : 1;
   const int nxv1 = nxch * vpcx, nyv1 = YCH * vpcy;        // vectors of one patch
   const int nxv = ppi * nxv1, nyv = ppi * nyv1;
+  // the plan's divisions go by the launcher's magic multipliers (every dividend here is far below 2^16).  A stacked
+  // window's X part has one or both of its two chunks: the divisor is then vpcx or the launcher's 2 * vpcx.
+  static_assert(!STACK || CT == 1, "stacked windows: two X chunks per workgroup");
+  const unsigned m_nxv1 = nxch == XCH ? a.m_nxv1 : a.m_vpcx;
   const bf16_t* xg = (const bf16_t*)a.x_tl + (size_t)g * a.x_gs;
   const bf16_t* yg = (const bf16_t*)a.dy_tl + (size_t)g * a.dy_gs;
   const size_t xpatch = (size_t)a.NCx * xtrows * 16, ypatch = (size_t)a.NCy * ytrows * 16;
@@ -825,12 +842,12 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx
 #pragma unroll
   for (int u = 0; u < XV; ++u) {
     int v = min(tid + u * NTHR, max(nxv, 1) - 1);
-    const int pp = (STACK && nxv1 > 0) ? v / nxv1 : 0;
+    const int pp = (STACK && nxv1 > 0) ? fastdiv1(v, nxv1, m_nxv1) : 0;
     v -= pp * nxv1;
-    int ch = v / vpcx, o = v - ch * vpcx;
+    int ch = fastdiv1(v, vpcx, a.m_vpcx), o = v - ch * vpcx;
     int row = o >> 1;
     xsrc[u] = ((nxch > 0 ? chunk0 : 0) + ch) * xtrows * 16 + o * 8;
-    if (xc) { const int hh = row / a.W; row = (hh + 1) * W2 + (row - hh * a.W) + 1; }   // pixel -> haloed-grid row
+    if (xc) { const int hh = fastdiv1(row, a.W, a.m_W); row = (hh + 1) * W2 + (row - hh * a.W) + 1; }   // pixel -> haloed-grid row
     xrow[u] = xc ? 0 : row;                    // compact rows always exist
     xdst[u] = (ch * WR + pp * Q + row) * RW + (o & 1) * 16;
     if constexpr (STACK) { xpp[u] = pp; xsrc[u] += pp * a.S * (int)xpatch; }     // (small maps: fits 32 bits by far)
@@ -838,12 +855,12 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx
 #pragma unroll
   for (int u = 0; u < YV; ++u) {
     int v = min(tid + u * NTHR, nyv - 1);
-    const int pp = STACK ? v / nyv1 : 0;
+    const int pp = STACK ? fastdiv1(v, nyv1, a.m_nyv1) : 0;
     v -= pp * nyv1;
-    int ch = v / vpcy, o = v - ch * vpcy;
+    int ch = fastdiv1(v, vpcy, a.m_vpcy), o = v - ch * vpcy;
     int row = o >> 1;
     ysrc[u] = (a.ych0 + ng * YCH + ch) * ytrows * 16 + o * 8;
-    if (yc) { const int hh = row / a.W; row = (hh + 1) * W2 + (row - hh * a.W) + 1; }   // pixel -> haloed-grid row
+    if (yc) { const int hh = fastdiv1(row, a.W, a.m_W); row = (hh + 1) * W2 + (row - hh * a.W) + 1; }   // pixel -> haloed-grid row
     yrow[u] = yc ? 0 : row;
     ydst[u] = (ch * WR + pp * Q + row) * RW + (o & 1) * 16;
     if constexpr (STACK) { ypp[u] = pp; ysrc[u] += pp * a.S * (int)ypatch; }
@@ -910,7 +927,7 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx
   __syncthreads();
   WTICK_DECL
 #ifdef DTA_TICKS
-  if (blockIdx.x == 17 && threadIdx.x == 0 && a.N == 64 && a.NCx > 8) g_wticks[6] = wt0_ - wentry_;      // entry -> loop
+  if (WTICK_GATE && threadIdx.x == 0) g_wticks[6] = wt0_ - wentry_;      // entry -> loop
 #endif
   // one iteration; RX_/RY_ = the register set that holds window it + 1 (and then receives window it + AHEAD)
 #define DTA_WGRAD_ITER(RX_, RY_, it)                                                                              \
@@ -969,9 +986,69 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx
 #ifdef DTA_TICKS
   const long long wloopend_ = clock64();
 #endif
-  // the odd-k waves hand their partial sums to their even-k partners through LDS (the staging buffers are free now:
-  // the loop ended on a barrier), two tap tiles per pass
-  float* red = reinterpret_cast<float*>(smem);
+  // partial[g][tap][c][s][n]: the S partial sums of one output row are contiguous for the reduction
+  float* out = a.partial + (size_t)g * 9 * a.Cpad * a.S * a.N + (size_t)s * a.N + ng * N;     // (a.N = ngr * N columns per row)
+  float* red = reinterpret_cast<float*>(smem);      // (the staging buffers are free now: the loop ended on a barrier)
+  if (!a.old_epilogue) {
+    // All eight waves: in passes of WGRAD_EPI_T taps every wave writes its partial tiles to an fp32 LDS image
+    // [tap][pair][k-slice][row c][column n]; after one barrier the 512 threads take 16-byte vectors (tap, c, 4 columns),
+    // add the KS partials -- ((slice 0 + slice 1) + slice 2) + slice 3, the order of the first epilogue below, so every
+    // slab element keeps its bits -- and write one 16-byte nontemporal store each: 9 (PAIRS = 2) or 18 (PAIRS = 4)
+    // dwordx4 stores per thread.  The first epilogue stored from the accumulator layout, 144 dword stores per lane on the
+    // PAIRS slice-0 waves only, and was bound by their issue rate (cycle stamps: 11-14 k cycles after 5-8 k of hand-over).
+    // Banks: a wave's ds_write_b32 puts each 32-lane half on the 32 consecutive dwords of one row (the halves, four rows
+    // apart, are separate lane groups), and the ds_read_b128 lane groups of the reader below (8 lanes per 128-byte row,
+    // then the next column tile -- a multiple of 256 B away -- then the next row) cover the four 64-byte quarters of the
+    // 256-byte bank row once each: conflict-free at the natural 128-byte pitch, so the rows are not padded.  (NTT = 4: the
+    // four column tiles of a row come before the next row and collide two by two on the read; that program is not on
+    // any measured path.)
+    constexpr int TILE = 32 * 32;
+    constexpr int VPT = PAIRS * 256 / NTHR;      // 16-byte vectors per thread and tap
+    const int wofs = (pair * KS + khalf) * TILE + 4 * (lane >> 5) * 32 + (lane & 31);
+#pragma unroll
+    for (int j0 = 0; j0 < 9; j0 += WGRAD_EPI_T) {
+      if (j0 > 0) __syncthreads();               // the previous pass has been read
+#pragma unroll
+      for (int jj = 0; jj < WGRAD_EPI_T; ++jj)
+        if (j0 + jj < 9) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) red[jj * 8 * TILE + wofs + ((r & 3) + 8 * (r >> 2)) * 32] = acc[j0 + jj][r];
+        }
+      __syncthreads();
+#ifdef DTA_TICKS
+      if (j0 + WGRAD_EPI_T >= 9 && WTICK_GATE && threadIdx.x == 0) g_wticks[7] = clock64() - wloopend_;      // last tap is in LDS
+#endif
+#pragma unroll
+      for (int jj = 0; jj < WGRAD_EPI_T; ++jj)
+        if (j0 + jj < 9) {
+#pragma unroll
+          for (int u = 0; u < VPT; ++u) {
+            const int v = tid + u * NTHR;        // (4 columns, column tile, row, channel tile), columns fastest
+            const int n4 = v & 7, ntv = (v >> 3) % NTT, cl = ((v >> 3) / NTT) & 31, ctv = v / (256 * NTT);
+            const f32x4* src = reinterpret_cast<const f32x4*>(red + (jj * 8 + (ctv * NTT + ntv) * KS) * TILE + cl * 32 + n4 * 4);
+            f32x4 sum = src[0];
+#pragma unroll
+            for (int q = 1; q < KS; ++q) sum += src[q * (TILE / 4)];
+            const int c = cg * CT * 32 + ctv * 32 + cl;
+            if (c < a.Cpad)
+              __builtin_nontemporal_store(sum, reinterpret_cast<f32x4*>(&out[((size_t)(j0 + jj) * a.Cpad + c) * a.S * a.N + ntv * 32 + n4 * 4]));
+          }
+        }
+    }
+#ifdef DTA_TICKS
+    if (WTICK_GATE && threadIdx.x == 0) {
+      g_wticks[14] = clock64() - wloopend_;      // ... + slab stores issued
+      __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
+      g_wticks[15] = clock64() - wloopend_;      // ... + slab stores performed
+    }
+#endif
+    return;
+  }
+  // The first epilogue (developer switch DTA_WGRAD_OLD_EPILOGUE; kept for the bit-identity test and kernel-level A/B):
+  // the odd-k waves hand their partial sums to their even-k partners through LDS, two tap tiles per pass, and the even-k
+  // (slice 0) waves store from the accumulator layout, 4 bytes per lane and instruction.  (Each pass's tiles are stored as
+  // they are summed -- measured equal to storing all nine after the last pass -- so that this branch does not modify the
+  // accumulators: with two epilogues that do, the register allocator spills every instantiation.)
 #pragma unroll
   for (int j0 = 0; j0 < 9; j0 += 2) {
     if (khalf != 0) {
@@ -988,30 +1065,20 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, const int bx
       for (int jj = 0; jj < 2; ++jj)
         if (j0 + jj < 9) {
 #pragma unroll
-          for (int q = 0; q < KS - 1; ++q)
+          for (int r = 0; r < 16; ++r) {
+            float sum = acc[j0 + jj][r];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j0 + jj][r] += red[(((pair * (KS - 1) + q) * 2 + jj) * 16 + r) * 64 + lane];
+            for (int q = 0; q < KS - 1; ++q) sum += red[(((pair * (KS - 1) + q) * 2 + jj) * 16 + r) * 64 + lane];
+            const int c = cg * CT * 32 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (c < a.Cpad) __builtin_nontemporal_store(sum, &out[((size_t)(j0 + jj) * a.Cpad + c) * a.S * a.N + nt * 32 + (lane & 31)]);
+          }
         }
     }
-    __syncthreads();
+    if (j0 + 2 < 9) __syncthreads();
   }
 #ifdef DTA_TICKS
-  if (blockIdx.x == 17 && threadIdx.x == 0 && a.N == 64 && a.NCx > 8) g_wticks[7] = clock64() - wloopend_;      // k-slice hand-over
-#endif
-  if (khalf != 0) return;
-  // partial[g][tap][c][s][n]: the S partial sums of one output row are contiguous for the reduction
-  float* out = a.partial + (size_t)g * 9 * a.Cpad * a.S * a.N + (size_t)s * a.N + ng * N;     // (a.N = ngr * N columns per row)
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int c = cg * CT * 32 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (c < a.Cpad) __builtin_nontemporal_store(acc[j][r], &out[((size_t)j * a.Cpad + c) * a.S * a.N + nt * 32 + (lane & 31)]);
-    }
-  }
-#ifdef DTA_TICKS
-  if (blockIdx.x == 17 && threadIdx.x == 0 && a.N == 64 && a.NCx > 8) {
-    g_wticks[14] = clock64() - wloopend_;      // ... + slab stores issued
+  if (WTICK_GATE && threadIdx.x == 0) {
+    g_wticks[7] = g_wticks[14] = clock64() - wloopend_;      // hand-over passes done = slab stores issued
     __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
     g_wticks[15] = clock64() - wloopend_;      // ... + slab stores performed
   }
@@ -1094,7 +1161,7 @@ static int resolve_wgrad_bf16(const WgradArgs& a, int G, int cgroups, WgradArgs&
   size_t stage = (size_t)(CT * 2 + NTT * 2) * a2.wr * RW;
   a2.dbuf = 2 * stage <= 160 * 1024;
   lds = (a2.dbuf ? 2 : 1) * stage;
-  if (lds < 48 * 1024) lds = 48 * 1024;   // the final reduction passes up to 6 x 2 tiles (8 KiB each) through LDS
+  if (lds < WGRAD_EPI_LDS) lds = WGRAD_EPI_LDS;   // the slab epilogue's image: WGRAD_EPI_T taps x 8 wave tiles (4 KiB each)
   if (lds > 160 * 1024) { dta_set_error("conv_wgrad(bf16): LDS need %zu B exceeds 160 KiB", lds); return 1; }
   a2.ppi = 1;
   static const bool no_stack = dev_getenv("DTA_NO_WGRAD_STACK") != nullptr;      // development A/B switches, read once
@@ -1115,8 +1182,17 @@ static int resolve_wgrad_bf16(const WgradArgs& a, int G, int cgroups, WgradArgs&
   stage = (size_t)(CT * 2 + NTT * 2) * a2.wr * RW;
   a2.dbuf = 2 * stage <= 160 * 1024;
   lds = (a2.dbuf ? 2 : 1) * stage;
-  if (lds < 48 * 1024) lds = 48 * 1024;
+  if (lds < WGRAD_EPI_LDS) lds = WGRAD_EPI_LDS;
   a2.cgroups = cgroups; a2.G = G;
+  {  // the staging plan's divisors (wgrad_bf16_body)
+    const int HWp = a.H * a.W, vpcx = a.x_compact ? HWp * 2 : a2.wr * 2, vpcy = a.y_compact ? HWp * 2 : a2.wr * 2;
+    a2.m_vpcx = fastdiv_magic(vpcx); a2.m_nxv1 = fastdiv_magic(CT * 2 * vpcx);
+    a2.m_vpcy = fastdiv_magic(vpcy); a2.m_nyv1 = fastdiv_magic(NTT * 2 * vpcy);
+    a2.m_W = fastdiv_magic(a.W);
+  }
+  // developer switch: the first slab epilogue.  Read per launch, unlike the plan switches above, so that one process of
+  // the developer library can run the same step through both epilogues (tests/test_wgrad_epilogue_gpu.py)
+  a2.old_epilogue = dev_getenv("DTA_WGRAD_OLD_EPILOGUE") != nullptr;
   a2.ngroups = a.N / (NTT * 32);
   total = cgroups * a2.ngroups * a.S * G;
   // two windows in flight in registers: the first conv's <2,2> (cycle stamps: loop 119.9 k -> 116.7 k cycles; the

@@ -62,6 +62,10 @@ struct WgradArgs {
   int ngroups;                        // bf16: output-column groups per (channel group, slab): a workgroup covers N / ngroups columns (0 = 1)
   int x_compact;                      // bf16, single band: X tiles are halo-free [patch][chunk][pixel][16]
   int y_compact;                      // likewise the dY tiles
+  // bf16, filled by the launcher (conv_bf16.hip: resolve_wgrad_bf16): magic multipliers of the staging plan's divisors
+  // (X vectors per patch with all of a workgroup's chunks, X / dY vectors per chunk, dY vectors per patch, map width)
+  unsigned m_nxv1, m_vpcx, m_nyv1, m_vpcy, m_W;
+  int old_epilogue;                   // developer switch DTA_WGRAD_OLD_EPILOGUE: hand-over passes + 4-byte slab stores
 };
 // bl = rows per band (multiple of 16), wr = bl + 2*(W+3) rounded up to 4 (mod 8), wr <= wr_max
 void wgrad_band_plan(int Q, int W, int wr_max, int* bl, int* wr, int* nbands);
