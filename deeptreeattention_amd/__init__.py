@@ -33,6 +33,10 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.levels     <->  src/models/multi_stage.py MultiStage.__init__ + create_datasets: which individuals
                                      each of the five levels trains on and in what order, the level labels, num_classes and
                                      the loss weights, from one resident integer table in a chain of at most four launches
+    deeptreeattention_amd.field      <->  src/data.py filter_data + src/megaplot.py format (create_grid, buffer_plots): which rows
+                                     of a raw NEON field table survive (per-row rules, the shaded individuals, one record
+                                     per individual) in a chain of five launches, and the 40 m plot code of every stem of a
+                                     contributed megaplot, by grid or by buffer, in one
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

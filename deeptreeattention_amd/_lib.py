@@ -122,6 +122,15 @@ LEVEL_MAX_SPECIES = 4096   # DTA_LEVEL_MAX_SPECIES
 LEVEL_HEAD, LEVEL_CONIFER, LEVEL_OAK, LEVEL_PLAIN = 0, 1, 2, 3   # DTA_LEVEL_HEAD ..
 
 
+# DTA_FIELD_* flag bits, DTA_FIELD_REASON_BAD_CODE, DTA_MEGAPLOT_*
+FIELD_COORDS, FIELD_GROWTH, FIELD_LIVE, FIELD_SHADED, FIELD_SUNNY, FIELD_TAXON_EXCLUDED = 1, 2, 4, 8, 16, 32
+FIELD_EVENT_DROPPED, FIELD_MULTIBOLE, FIELD_KNOWN_ERROR, FIELD_PLOT_EXCLUDED, FIELD_SITE_EXCLUDED = 64, 128, 256, 512, 1024
+FIELD_REASON_BAD_CODE = 255
+MEGAPLOT_GRID, MEGAPLOT_BUFFER = 0, 1
+MEGAPLOT_BUFFER_MAX = 65536   # DTA_MEGAPLOT_BUFFER_MAX
+MEGAPLOT_CHUNK = 1024   # DTA_MEGAPLOT_CHUNK
+
+
 class LevelTables(C.Structure):     # dta_level_tables
     _fields_ = [("individuals", C.c_longlong), ("records", C.c_longlong), ("species", C.c_int), ("years", C.c_int)] + \
                [(n, C.c_void_p) for n in ("ind", "year", "sp", "rank", "first", "m", "present", "cls", "lmap", "species_order",
@@ -449,6 +458,14 @@ def lib():
         L.dta_level_workspace_bytes.argtypes = [C.c_longlong, C.c_longlong, C.c_int, C.c_int]
         L.dta_level_build.restype = C.c_int
         L.dta_level_build.argtypes = [C.POINTER(LevelTables), C.POINTER(LevelConfig), C.POINTER(LevelOut), vp, C.c_size_t, vp]
+        # field records to canopy points: the NEON row filter and the megaplot plot codes (field.hip)
+        L.dta_field_workspace_bytes.restype = C.c_size_t
+        L.dta_field_workspace_bytes.argtypes = [C.c_longlong, C.c_longlong]
+        L.dta_field_filter.restype = C.c_int
+        L.dta_field_filter.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_longlong, C.c_double, C.c_double, vp, vp, vp, vp, vp,
+                                       vp, C.c_size_t, vp]
+        L.dta_megaplot_plots.restype = C.c_int
+        L.dta_megaplot_plots.argtypes = [vp, C.c_longlong, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -45,7 +45,8 @@ assign_np is the definition; CrownBoxes.assign equals it bit for bit.  The devic
 stems of the plots its workgroup of 256 stems touches: N x (boxes + stems of a plot) in all, linear in practice because
 plots are 40 m cells, and quadratic in the stems of one plot if a caller makes a whole tile one plot.
 Out of scope: DeepForest itself, reading rasters or shapefiles, rasterio.windows.from_bounds (a caller keeps its own pixel
-boxes and indexes them with `box`), the megaplot grid of src/megaplot.py, crown polygons other than boxes.
+boxes and indexes them with `box`), crown polygons other than boxes.  The `point_plot` codes of a contributed megaplot
+(the grid and the buffers of src/megaplot.py) come from field.megaplot_plots.
 """
 import collections
 import math

@@ -1211,6 +1211,67 @@ size_t dta_level_workspace_bytes(long long individuals, long long records, int s
 int dta_level_build(const dta_level_tables* tables, const dta_level_config* config, const dta_level_out* out, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- Field records to canopy points: which rows of a raw NEON field table survive (the reference's filter_data,
+ * src/data.py:22-106) and the plot code of every stem of a contributed megaplot (megaplot.format, src/megaplot.py:28-90:
+ * create_grid with gpd.sjoin, buffer_plots).  deeptreeattention_amd/field.py: filter_np and plots_np are the definitions
+ * (they state the rules in full) and the kernels equal them bit for bit.
+ *
+ * dta_field_filter.  All tables on the device, one entry per row of the field table, in frame order:
+ *   individual: int [rows], the code of the row's individual, 0 .. individuals - 1 (the rank of its name among the sorted
+ *               unique names); event: int [rows], the rank of the row's event name, >= 0; height, diameter: double [rows],
+ *               NaN = missing; flags: unsigned short [rows], the DTA_FIELD_* bits below, made from the table's strings.
+ * reason_out[r] is the first step that drops row r, 0 = kept (keep_out[r] = 1):
+ *   1 no COORDS; 2 no GROWTH; 3 no LIVE; 4 over the rows that passed 1-3 the individual has a SHADED row and no SUNNY row;
+ *   5 not (height > min_height or height is NaN); 6 not (diameter > min_stem_diameter), NaN fails; 7 TAXON_EXCLUDED;
+ *   8 EVENT_DROPPED; 9 not the individual's record: among the rows that passed 1-8, an individual with a height keeps the row
+ *   of its maximum height (-0.0 equals +0.0), one with none the row of its largest event code, the lowest row among equals
+ *   either way; 10 MULTIBOLE; 11 KNOWN_ERROR; 12 PLOT_EXCLUDED; 13 SITE_EXCLUDED.
+ *   DTA_FIELD_REASON_BAD_CODE: an individual code outside 0 .. individuals - 1 or an event code below 0; such a row takes
+ *   part in nothing and is counted in errors_out (int [1], may be NULL).
+ * rows_out: long long [rows]: the kept rows, first those of the individuals chosen by height, ascending by individual code,
+ * then those chosen by event, ascending by individual code; -1 behind them.  count_out: long long [1], how many.
+ * workspace: dta_field_workspace_bytes(rows, individuals) bytes, 16-byte aligned (0: sizes out of range).  Five launches
+ * and one memset on the stream, no allocation, no host synchronisation.  Integer OR / max atomics at device scope only,
+ * whose result does not depend on their order: reruns are bit-identical.  Refused on the host, before a launch: a null
+ * pointer other than errors_out; rows < 1 or >= 2^31; individuals < 1 or > rows; a threshold that is NaN; a workspace that
+ * is too small or misaligned. */
+#define DTA_FIELD_COORDS 1
+#define DTA_FIELD_GROWTH 2
+#define DTA_FIELD_LIVE 4
+#define DTA_FIELD_SHADED 8
+#define DTA_FIELD_SUNNY 16
+#define DTA_FIELD_TAXON_EXCLUDED 32
+#define DTA_FIELD_EVENT_DROPPED 64
+#define DTA_FIELD_MULTIBOLE 128
+#define DTA_FIELD_KNOWN_ERROR 256
+#define DTA_FIELD_PLOT_EXCLUDED 512
+#define DTA_FIELD_SITE_EXCLUDED 1024
+#define DTA_FIELD_REASON_BAD_CODE 255
+size_t dta_field_workspace_bytes(long long rows, long long individuals);
+int dta_field_filter(const int* individual, const int* event, const double* height, const double* diameter,
+                     const unsigned short* flags, long long rows, long long individuals, double min_stem_diameter,
+                     double min_height, unsigned char* keep_out, unsigned char* reason_out, long long* rows_out,
+                     long long* count_out, int* errors_out, void* workspace, size_t workspace_bytes, void* stream);
+/* dta_megaplot_plots.  points: double [n][2] (x, y) on the device; code_out: int [n]; one launch, no workspace, no atomics.
+ *   DTA_MEGAPLOT_GRID:   xs: double [nx] and ys: double [ny] on the device, ascending in steps of `cell` (the caller's
+ *     np.arange(min, max + cell, cell) over the points' bounds).  Cell (i, j) has the code i * ny + j and is the closed
+ *     rectangle xs[i] - cell <= x <= xs[i], ys[j] <= y <= ys[j] + cell, each bound rounded once (the reference's
+ *     box(x0, y0, x0 - 40, y0 + 40) does lie to the LEFT of x0).  A point takes the lowest code among the cells that hold it
+ *     (the device looks at the two columns and rows on either side of floor((x - xs[0]) / cell), with these comparisons), -1
+ *     when none does or a coordinate is not finite.
+ *   DTA_MEGAPLOT_BUFFER: code[j] = the highest i with (xi - xj) * (xi - xj) + (yi - yj) * (yi - yj) <= cell * cell, every
+ *     product and sum rounded on its own (no FMA); -1 for a stem with a coordinate that is not finite.  n * n compares: n is
+ *     at most DTA_MEGAPLOT_BUFFER_MAX.  xs and ys are not read.
+ * Refused on the host, before the launch: a null points or code_out; a rule other than the two; a cell that is not finite
+ * or <= 0 (or whose square is not finite, buffer rule); n < 1, n >= 2^31 (grid) or n > DTA_MEGAPLOT_BUFFER_MAX (buffer);
+ * grid rule: a null table, nx or ny < 1, nx * ny >= 2^31. */
+#define DTA_MEGAPLOT_GRID 0
+#define DTA_MEGAPLOT_BUFFER 1
+#define DTA_MEGAPLOT_BUFFER_MAX 65536
+#define DTA_MEGAPLOT_CHUNK 1024             /* stems staged through LDS at a time */
+int dta_megaplot_plots(const double* points, long long n, int rule, double cell, const double* xs, int nx, const double* ys,
+                       int ny, int* code_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
