@@ -37,6 +37,11 @@ The package mirrors the reference's module names for this path only:
                                      of a raw NEON field table survive (per-row rules, the shaded individuals, one record
                                      per individual) in a chain of five launches, and the 40 m plot code of every stem of a
                                      contributed megaplot, by grid or by buffer, in one
+    deeptreeattention_amd.evaluate   <->  src/models/multi_stage.py evaluation_scores + src/main.py evaluate_crowns +
+                                     src/metrics.py: the experiment report from one grouped confusion table counted on the
+                                     device (one launch per batch) and reduced in one launch -- per-site micro / macro,
+                                     per-species accuracy / precision, the within-site and within-genus shares of the
+                                     errors -- plus the first row per individual and the novel-species scores
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

@@ -466,6 +466,15 @@ def lib():
                                        vp, C.c_size_t, vp]
         L.dta_megaplot_plots.restype = C.c_int
         L.dta_megaplot_plots.argtypes = [vp, C.c_longlong, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, vp, vp]
+        # crown-level evaluation: the grouped confusion table, its report, first rows per individual, novel scores (evaluate.hip)
+        L.dta_eval_count.restype = C.c_int
+        L.dta_eval_count.argtypes = [vp, vp, vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_longlong, C.c_int, vp, vp, vp]
+        L.dta_eval_report.restype = C.c_int
+        L.dta_eval_report.argtypes = [vp, C.c_int, C.c_longlong, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.dta_first_rows.restype = C.c_int
+        L.dta_first_rows.argtypes = [vp, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp]
+        L.dta_novel_scores.restype = C.c_int
+        L.dta_novel_scores.argtypes = [vp, C.c_longlong, C.c_int, vp, vp, vp, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

@@ -1272,6 +1272,61 @@ int dta_field_filter(const int* individual, const int* event, const double* heig
 int dta_megaplot_plots(const double* points, long long n, int rule, double cell, const double* xs, int nx, const double* ys,
                        int ny, int* code_out, void* stream);
 
+/* ---- Crown-level evaluation: the reference's experiment report (MultiStage.evaluation_scores, multi_stage.py:436-485;
+ * TreeModel.evaluate_crowns, main.py:265-333; site_confusion / genus_confusion / novel_prediction, src/metrics.py) as
+ * functions of one grouped confusion table conf[g][t][p] = counted crowns of group g with label t and prediction p.
+ * deeptreeattention_amd/evaluate.py: count_np, report_np, first_per_individual_np are the definitions and the kernels equal
+ * them bit for bit.  All arrays on the device; no allocation, no host synchronisation.
+ *
+ * dta_eval_count.  labels, preds: long long [rows]; group: int [rows] (group_is_64 = 0) or long long [rows] (1), NULL = all
+ * rows in group 0; mask: unsigned char [rows], NULL = all rows; conf: long long [groups][n_species][n_species] and tally:
+ * long long [2], both ACCUMULATED into (the caller zeroes them once).  A row with mask 0 is neither counted nor tallied; a
+ * row whose label or prediction is outside 0 .. n_species - 1 or whose group is outside 0 .. groups - 1 adds one to tally[1];
+ * every other row adds one to conf[group][label][pred] and to tally[0].  One launch; 64-bit integer atomic adds only, so the
+ * result does not depend on their order.  form: DTA_EVAL_COUNT_PLAIN, one atomic per counted row; DTA_EVAL_COUNT_COMBINE,
+ * the lanes of a wave that hold the same entry are added up first (DTA_EVAL_COMBINE_ROUNDS first-lane / ballot rounds, what
+ * is left goes out singly): the same table either way.  1 <= n_species <= DTA_EVAL_MAX_SPECIES, groups >= 1 and
+ * groups * n_species * n_species <= 2^31 - 1 (an entry's index is an int); 1 <= rows <= 2^31 - 1.
+ *
+ * dta_eval_report.  conf as above (entries >= 0).  One launch of groups + 1 workgroups: workgroup g reduces plane g,
+ * workgroup `groups` the sum of all planes (the pooled row).  Row r of
+ *   counts  long long [groups + 1][8]: total, correct, wrong, within_site, cross_site, within_genus, cross_genus, species
+ *           seen (label sum > 0);
+ *   scores  double [groups + 1][4]: micro = correct / total, macro = the sum of the seen species' accuracies, added in class
+ *           order, / their number, within_site / wrong, within_genus / wrong;
+ *   accuracy, precision double, support long long [groups + 1][n_species] (all three or none): diagonal / label sum,
+ *           diagonal / prediction sum, label sum.
+ * Every quotient is one IEEE division of two integers converted to double; a zero denominator gives 0.0.  site_masks:
+ * unsigned long long [n_species][site_words], 1 <= site_words <= DTA_EVAL_MAX_SITE_WORDS, bit b of a species = it occurs on
+ * site b; an error (t != p) is within_site when the two masks share a bit.  genus: int [n_species]; an error is within_genus
+ * when the two ids are equal.  Either may be NULL: its two counts are 0 and its share 0.0.
+ *
+ * dta_first_rows.  ids: int [rows] (ids_is_64 = 0) or long long [rows] (1); first_out: unsigned char [rows] = 1 where the row
+ * is the lowest row of its id (the reference's groupby("individual").head(1)), 0 elsewhere and for an id outside
+ * 0 .. n_ids - 1; workspace: int [n_ids].  One fill and two launches (an integer atomic min of the row, then a compare).
+ *
+ * dta_novel_scores.  logits: float [rows][classes], 1 <= classes <= DTA_EVAL_MAX_SPECIES.  One launch, one wave per row,
+ * on dta_softmax_top2's row body: label_out long long [rows] and softmax_out float [rows] are that entry's top_idx[:, 0] and
+ * top_score[:, 0] (a row with a NaN: -1 and -1.0); top_out float [rows] is the row's largest logit (NaN for a row with a NaN).
+ *
+ * Refused on the host, before a launch: a null pointer other than those named optional; a size outside the ranges above;
+ * accuracy, precision and support not all given or all NULL; site_masks with site_words outside its range. */
+#define DTA_EVAL_MAX_SPECIES 1020
+#define DTA_EVAL_MAX_SITE_WORDS 4
+#define DTA_EVAL_COUNT_PLAIN 0
+#define DTA_EVAL_COUNT_COMBINE 1
+#define DTA_EVAL_COMBINE_ROUNDS 4
+int dta_eval_count(const long long* labels, const long long* preds, const void* group, int group_is_64,
+                   const unsigned char* mask, long long rows, int n_species, long long groups, int form, long long* conf,
+                   long long* tally, void* stream);
+int dta_eval_report(const long long* conf, int n_species, long long groups, const unsigned long long* site_masks,
+                    int site_words, const int* genus, long long* counts, double* scores, double* accuracy,
+                    double* precision, long long* support, void* stream);
+int dta_first_rows(const void* ids, int ids_is_64, long long rows, long long n_ids, unsigned char* first_out, int* workspace,
+                   void* stream);
+int dta_novel_scores(const float* logits, long long rows, int classes, long long* label_out, float* top_out,
+                     float* softmax_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
