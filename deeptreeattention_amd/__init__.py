@@ -16,6 +16,10 @@ The package mirrors the reference's module names for this path only:
     deeptreeattention_amd.dead       <->  src/models/dead.py + src/predict.py predict_tile(filter_dead=True): the normalised,
                                      resized RGB crop of every crown box from a resident uint8 raster (one launch), the
                                      alive/dead score of the classifier's logits, and the rule that blanks dead crowns
+    deeptreeattention_amd.dead_train <->  train_dead.py + src/models/dead.py AliveDead: the labelled images resident once, a
+                                     batch (normalise, resize, flip, labels) in one launch, the sigmoid cross-entropy with
+                                     its gradient and confusion counts in one launch, the epoch loop, the precision-recall
+                                     curve behind dead_threshold (also reachable as dead.<name>)
     deeptreeattention_amd.reflectance  <->  src/Hyperspectral.py:138-219 generate_raster / calc_clip_index: the band mask, the
                                      clip window and the band-first transpose between a pixel-interleaved reflectance cube
                                      and the resident raster (DenseRaster.from_reflectance: one launch per strip of rows)
@@ -55,8 +59,9 @@ from .dense import predict_windows_multistage, predict_map_multistage, crown_res
 from .dense import predict_windows_metadata, predict_map_metadata  # noqa: F401
 from .dense import crop_boxes, predict_crops, predict_crops_multistage, predict_crops_metadata  # noqa: F401
 from .treedata import CropPool, PoolView, LevelViews, epoch_order_np  # noqa: F401
+from .dead_train import ImagePool, DeadAccumulator  # noqa: F401
 
-__all__ = ["CropPool", "PoolView", "LevelViews", "epoch_order_np","Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
+__all__ = ["ImagePool", "DeadAccumulator", "CropPool", "PoolView", "LevelViews", "epoch_order_np","Hang2020", "set_default_precision", "get_default_precision", "Hierarchy", "scores_from_confusion",
            "validate", "validate_multistage", "DenseRaster", "window_origins", "predict_windows", "predict_map",
            "predict_windows_multistage", "predict_map_multistage", "crown_resolve",
            "crop_boxes", "predict_crops", "predict_crops_multistage", "predict_crops_metadata"]

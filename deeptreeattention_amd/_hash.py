@@ -12,6 +12,8 @@ import numpy as np
 GOLDEN = 0x9E3779B97F4A7C15
 M64 = (1 << 64) - 1
 STREAM_ABUNDANCE_KEEP, STREAM_ABUNDANCE_DRAW, STREAM_SPLIT = 0, 1, 0      # (_lib.LEVEL_STREAM, _lib.EPOCH_ORDER_STREAM + level)
+STREAM_DEAD_FLIP = 3           # dead.flips_np (_lib.DEAD_FLIP_STREAM); the image pool's order is level id DEAD_ORDER_LEVEL
+DEAD_ORDER_LEVEL = 63          # _lib.DEAD_ORDER_LEVEL: stream EPOCH_ORDER_STREAM + 63
 
 
 def mix_int(z):

@@ -99,6 +99,10 @@ CROWN_WAVE_CELLS = 1024   # DTA_CROWN_WAVE_CELLS
 ELEM_F32, ELEM_BF16, ELEM_F16 = 0, 1, 2   # DTA_ELEM_*
 RGB_CROPS_MAX_GROUPS = 1024   # DTA_RGB_CROPS_MAX_GROUPS
 RGB_CROPS_MAX_SIZE = 512   # DTA_RGB_CROPS_MAX_SIZE
+DEAD_FLIP_STREAM = 3   # DTA_DEAD_FLIP_STREAM
+DEAD_ORDER_LEVEL = 63   # DTA_DEAD_ORDER_LEVEL
+DEAD_ACC_WORDS = 7   # DTA_DEAD_ACC_WORDS
+DEAD_LOSS_MAX_ROWS = 1 << 24   # DTA_DEAD_LOSS_MAX_ROWS
 REFLECTANCE_MAX_BANDS = 1024   # DTA_REFLECTANCE_MAX_BANDS
 BOUNDARY_EDGE_CHUNK = 1024   # DTA_BOUNDARY_EDGE_CHUNK
 BOUNDARY_MAX_EDGES = 1 << 20   # DTA_BOUNDARY_MAX_EDGES
@@ -423,6 +427,13 @@ def lib():
                                     C.c_int, C.c_int, vp, vp, vp]
         L.dta_dead_head.restype = C.c_int
         L.dta_dead_head.argtypes = [vp, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp]
+        # training the alive/dead classifier: a batch of a resident image pool, and the loss with its gradient (dead_train.hip)
+        L.dta_image_pool_batch.restype = C.c_int
+        L.dta_image_pool_batch.argtypes = [vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, C.c_int, C.c_longlong, C.c_longlong,
+                                           vp, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_int, c_float_p, c_float_p, C.c_int,
+                                           C.c_int, vp, vp, vp]
+        L.dta_dead_loss.restype = C.c_int
+        L.dta_dead_loss.argtypes = [vp, C.c_int, vp, C.c_longlong, vp, vp, vp, vp, vp]
         # reflectance cube -> resident raster: band selection, window, min-max and transpose in one pass (reflectance.hip)
         L.dta_reflectance_normalise.restype = C.c_int
         L.dta_reflectance_normalise.argtypes = [C.POINTER(ReflectanceDesc), vp, vp, C.c_int, vp, vp]

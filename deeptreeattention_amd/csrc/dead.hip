@@ -12,6 +12,7 @@
 //   k_dead_head   one thread per crown of a batch: sigmoid, softmax over the two classes, max and argmax (a tie: 0).
 #include "../../include/dta_hip.h"
 #include "common.h"
+#include "rgb_crops_dev.h"       // the tables, the row blend and the store loop: shared with dead_train.hip's pool batches
 
 // the definition's float32 operations one by one (the weights and the four-term blend; the source position alone is one
 // fused multiply-add, written as such)
@@ -19,17 +20,8 @@
 
 namespace dta {
 
-constexpr int RC_THREADS = 256;
 constexpr int RC_MAX_GROUPS = DTA_RGB_CROPS_MAX_GROUPS;
 constexpr int RC_MAX_SIZE = DTA_RGB_CROPS_MAX_SIZE;
-constexpr int RC_MAX_CHANNELS = 4;
-constexpr int RC_UNIT_ELEMS = 65536;                // a unit of work: about this many outputs (whole output rows of a crown) ...
-constexpr int RC_MIN_UNIT_ELEMS = 8192;             // ... fewer, down to this, where the crowns are too few to give every workgroup one
-constexpr int RC_NORM_BYTES = RC_MAX_CHANNELS * 256 * 4;
-
-struct ColEntry { int x0; int dxc; float lx, omlx; };    // dxc: (x1 - x0) | (channel of the element << 1)
-struct RowEntry { int a, b; float ly, omly; };           // a, b: offsets of the two source rows' first box column in a plane
-static_assert(sizeof(ColEntry) == 16 && sizeof(RowEntry) == 16, "one ds_read_b128 each");
 
 struct CropArgs {
   const unsigned char* ras; int C, H, W;
@@ -40,49 +32,6 @@ struct CropArgs {
   int rb, units;                   // output rows per unit; units per crown
   long long total;                 // n * units
 };
-
-template <int FMT> struct Elem;
-template <> struct Elem<FMT_F32> { typedef float T; __device__ static __forceinline__ float cvt(float v) { return v; } };
-template <> struct Elem<FMT_BF16> { typedef unsigned short T; __device__ static __forceinline__ unsigned short cvt(float v) { return f2bf(v); } };
-template <> struct Elem<FMT_F16> {
-  typedef unsigned short T;
-  __device__ static __forceinline__ unsigned short cvt(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
-};
-
-template <int FMT, int VW>
-__device__ __forceinline__ void store_elems(void* out, size_t at, const float (&v)[VW]) {
-  typedef typename Elem<FMT>::T T;
-  T* p = (T*)out + at;
-  if constexpr (VW == 1) {
-    *p = Elem<FMT>::cvt(v[0]);
-  } else if constexpr (FMT == FMT_F32) {
-    static_assert(VW == 4, "");
-    f32x4 q = {v[0], v[1], v[2], v[3]};
-    *(f32x4*)p = q;
-  } else {
-    static_assert(VW == 8, "");
-    u32x4 q;
-    q.x = (unsigned)Elem<FMT>::cvt(v[0]) | ((unsigned)Elem<FMT>::cvt(v[1]) << 16);
-    q.y = (unsigned)Elem<FMT>::cvt(v[2]) | ((unsigned)Elem<FMT>::cvt(v[3]) << 16);
-    q.z = (unsigned)Elem<FMT>::cvt(v[4]) | ((unsigned)Elem<FMT>::cvt(v[5]) << 16);
-    q.w = (unsigned)Elem<FMT>::cvt(v[6]) | ((unsigned)Elem<FMT>::cvt(v[7]) << 16);
-    *(u32x4*)p = q;
-  }
-}
-
-// (1 - lx) * p(c, y, x0) + lx * p(c, y, x1) for a lane's VW columns of the source row at offset `row` of a plane
-template <int VW>
-__device__ __forceinline__ void blend_row(float (&h)[VW], const ColEntry (&ce)[VW], int row, int p, const unsigned char* ras,
-                                          size_t plane, const float* nt) {
-#pragma unroll
-  for (int q = 0; q < VW; ++q) {
-    const int ch = p + (ce[q].dxc >> 1);
-    const unsigned char* src = ras + (size_t)ch * plane + row;
-    const float* t = nt + ch * 256;
-    const int xa = ce[q].x0, xb = xa + (ce[q].dxc & 1);
-    h[q] = ce[q].omlx * t[src[xa]] + ce[q].lx * t[src[xb]];
-  }
-}
 
 // CL: channels_last memory ([n][i][j][c]: a line is one output row of S * C elements), otherwise [n][c][i][j] (a line is
 // one output row of one channel).  VEC: 16-byte stores; the host picks it only where every line starts 16-byte aligned.
@@ -99,13 +48,8 @@ __global__ __launch_bounds__(RC_THREADS) void k_rgb_crops(CropArgs a) {
   const int planes = CL ? 1 : C;                   // lines per output row
   const size_t plane = (size_t)H * W;
   const size_t crown_elems = (size_t)C * S * S;
-  for (int k = tid; k < C * 256; k += RC_THREADS)  // ToTensor, then Normalize: two correctly rounded float32 divisions
-    nt[k] = ((float)(k & 255) / 255.f - a.mean[k >> 8]) / a.stdv[k >> 8];
-  // this lane's place: TPR lanes side by side on a line, RG lines at a time
-  const int VPL = L / VW;                          // (VEC: L is a multiple of VW)
-  const int TPR = VPL < RC_THREADS ? VPL : RC_THREADS;
-  const int RG = RC_THREADS / TPR;
-  const int rg = tid / TPR, jv0 = tid - rg * TPR;
+  norm_table(nt, C, a.mean, a.stdv, tid);
+  const LanePlace z = lane_place(L, VW, tid);
   const long long u0 = a.total * (long long)blockIdx.x / (long long)gridDim.x;
   const long long u1 = a.total * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
   long long crown = -1;
@@ -122,90 +66,14 @@ __global__ __launch_bounds__(RC_THREADS) void k_rgb_crops(CropArgs a) {
       r0 = r0 > 0 ? r0 : 0; c0 = c0 > 0 ? c0 : 0;
       r1 = r1 < H ? r1 : H; c1 = c1 < W ? c1 : W;
       ok = b2 > b0 && b3 > b1 && r1 > r0 && c1 > c0;
-      if (ok) {                                    // 0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W
-        const int h = (int)(r1 - r0), w = (int)(c1 - c0);
-        const int base = (int)r0 * W + (int)c0;    // < H * W <= 2^31 - 1
-        const float sy = (float)h / (float)S, sx = (float)w / (float)S;
-        for (int i = tid; i < S; i += RC_THREADS) {
-          float f = __builtin_fmaf(sy, (float)i + 0.5f, -0.5f);     // fused, as torch's CPU kernel has it (dead.py)
-          f = f > 0.f ? f : 0.f;
-          int y0 = (int)f;
-          y0 = y0 < h - 1 ? y0 : h - 1;            // inside the clipped box whatever the rounding
-          const int y1 = y0 + 1 < h - 1 ? y0 + 1 : h - 1;
-          const float ly = f - (float)y0;
-          RowEntry e;
-          e.a = base + y0 * W; e.b = base + y1 * W; e.ly = ly; e.omly = 1.f - ly;
-          rowt[i] = e;
-        }
-        for (int k = tid; k < L; k += RC_THREADS) {
-          const int j = CL ? k / C : k, ch = CL ? k - j * C : 0;
-          float f = __builtin_fmaf(sx, (float)j + 0.5f, -0.5f);
-          f = f > 0.f ? f : 0.f;
-          int x0 = (int)f;
-          x0 = x0 < w - 1 ? x0 : w - 1;
-          const int x1 = x0 + 1 < w - 1 ? x0 + 1 : w - 1;
-          const float lx = f - (float)x0;
-          ColEntry e;
-          e.x0 = x0; e.dxc = (x1 - x0) | (ch << 1); e.lx = lx; e.omlx = 1.f - lx;
-          colt[k] = e;
-        }
-      }
+      if (ok)                                      // 0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W; the base is < H * W <= 2^31 - 1
+        build_tables<CL>(rowt, colt, S, C, L, (int)(r1 - r0), (int)(c1 - c0), (int)r0 * W + (int)c0, W, false, tid);
       __syncthreads();                             // (the first time round also: the normalisation table is complete)
       if (unit == 0 && tid == 0) a.valid[n] = ok ? 1 : 0;      // the crown's first unit belongs to one workgroup
     }
     const int i0 = unit * a.rb;
     const int i1 = i0 + a.rb < S ? i0 + a.rb : S;
-    const size_t obase = (size_t)n * crown_elems;
-    if (rg >= RG) continue;                        // lanes that do not fill another line (no barrier depends on them below)
-    // this lane's rows of the unit: consecutive ones, so that a blended source row serves every output row between it and
-    // its neighbour (an upsampled crown reads each source sample once per lane, not four per output)
-    const int chunk = (i1 - i0 + RG - 1) / RG;
-    const int ia = i0 + rg * chunk;
-    const int ib = ia + chunk < i1 ? ia + chunk : i1;
-    for (int jv = jv0; jv < VPL; jv += TPR) {
-      ColEntry ce[VW];
-      if (ok) {
-#pragma unroll
-        for (int q = 0; q < VW; ++q) ce[q] = colt[jv * VW + q];
-      }
-      for (int p = 0; p < planes; ++p) {
-        int ca = -1, cb = -1;                      // the source rows ha / hb hold (offsets are >= 0)
-        float ha[VW], hb[VW];
-#pragma unroll
-        for (int q = 0; q < VW; ++q) ha[q] = hb[q] = 0.f;
-        for (int i = ia; i < ib; ++i) {
-          float v[VW];
-          if (ok) {
-            const RowEntry re = rowt[i];
-            if (re.a != ca) {                      // the rows only move down: the new upper row is the old lower one, or new
-              if (re.a == cb) {
-#pragma unroll
-                for (int q = 0; q < VW; ++q) ha[q] = hb[q];
-              } else {
-                blend_row<VW>(ha, ce, re.a, p, a.ras, plane, nt);
-              }
-              ca = re.a;
-            }
-            if (re.b != cb) {
-              if (re.b == ca) {                    // y1 == y0: the box's last row (or its only one)
-#pragma unroll
-                for (int q = 0; q < VW; ++q) hb[q] = ha[q];
-              } else {
-                blend_row<VW>(hb, ce, re.b, p, a.ras, plane, nt);
-              }
-              cb = re.b;
-            }
-#pragma unroll
-            for (int q = 0; q < VW; ++q) v[q] = re.omly * ha[q] + re.ly * hb[q];
-          } else {
-#pragma unroll
-            for (int q = 0; q < VW; ++q) v[q] = 0.f;
-          }
-          const size_t line = CL ? (size_t)i : (size_t)p * S + i;
-          store_elems<FMT, VW>(a.out, obase + line * L + (size_t)jv * VW, v);
-        }
-      }
-    }
+    write_rows<FMT, CL, VW>(ok, a.ras, plane, nt, rowt, colt, a.out, (size_t)n * crown_elems, i0, i1, S, L, planes, z);
   }
 }
 
@@ -271,16 +139,7 @@ extern "C" int dta_rgb_crops(const unsigned char* raster, int channels, int heig
   for (int c = 0; c < RC_MAX_CHANNELS; ++c) { a.mean[c] = c < channels ? mean[c] : 0.f; a.stdv[c] = c < channels ? std[c] : 1.f; }
   a.out = out; a.valid = out_valid;
   const int row_elems = size * channels;
-  int rb = (RC_UNIT_ELEMS + row_elems - 1) / row_elems;
-  rb = rb < size ? rb : size;
-  if (n * ((size + rb - 1) / rb) < RC_MAX_GROUPS) {             // deeptreeattention_amd/dead.py: launch_plan is this rule
-    const int want = (int)((RC_MAX_GROUPS + n - 1) / n);        // units per crown that would fill the launch
-    int least = (RC_MIN_UNIT_ELEMS + row_elems - 1) / row_elems;
-    least = least < rb ? least : rb;
-    const int fill = (size + want - 1) / want;
-    rb = fill > least ? fill : least;
-  }
-  a.rb = rb;
+  a.rb = rgb_crops_rows_per_unit(n, size, channels, RC_MAX_GROUPS);
   a.units = (size + a.rb - 1) / a.rb;
   a.total = n * a.units;
   const int line = channels_last ? row_elems : size, vw = 16 / bytes;

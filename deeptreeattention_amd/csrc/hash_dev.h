@@ -6,7 +6,9 @@
 //   1        HASH_STREAM_ABUNDANCE_DRAW   abundance: the species it is drawn again as
 //   0        HASH_STREAM_SPLIT            split search: the order of the candidate plots (its counters are its own)
 //   2        DTA_LEVEL_STREAM             levels: the record shuffle of level 2                                  (dta_hip.h)
+//   3        DTA_DEAD_FLIP_STREAM         dead_train: is the image flipped (HASH_STREAM_DEAD_FLIP)               (dta_hip.h)
 //   16..79   DTA_EPOCH_ORDER_STREAM + level id (below DTA_EPOCH_ORDER_MAX_LEVEL_ID): the epoch orders            (dta_hip.h)
+//            level id 63 (DTA_DEAD_ORDER_LEVEL, stream 79): the alive/dead image pool's order
 #pragma once
 #include "common.h"
 

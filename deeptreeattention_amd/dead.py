@@ -49,6 +49,18 @@ MIN_UNIT_ELEMS = 8192            # RC_MIN_UNIT_ELEMS: ... fewer, down to this, w
 
 DeadPrediction = collections.namedtuple("DeadPrediction", "label score valid")
 
+# training the classifier (dead_train.py: the resident image pool, the loss, train_dead.py's loop, the precision-recall
+# curve) is reachable from here by name; that module builds on this one, so it is imported on first use
+_TRAIN = ("ImagePool", "DeadAccumulator", "loss", "fit", "validate", "pool_batch_np", "flips_np", "loss_np", "report_np",
+          "pr_curve_np", "threshold_for_precision")
+
+
+def __getattr__(name):
+    if name in _TRAIN:
+        from . import dead_train
+        return getattr(dead_train, name)
+    raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))
+
 
 def _host(a):
     return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)

@@ -961,6 +961,52 @@ int dta_rgb_crops(const unsigned char* raster, int channels, int height, int wid
 int dta_dead_head(const void* logits, int dtype, long long rows, long long offset, long long* out_label, float* out_score,
                   void* stream);
 
+/* ---- Training the alive/dead classifier from a resident image pool (train_dead.py; src/models/dead.py: AliveDead -- an
+ * ImageFolder of small RGB images, ToTensor, Normalize, Resize([224, 224]), RandomHorizontalFlip, and the loss
+ * F.cross_entropy(F.sigmoid(logits), y)).  deeptreeattention_amd/dead.py: pool_batch_np, flips_np and loss_np are the
+ * definitions.
+ *
+ * dta_image_pool_batch: one batch, crops and labels, in ONE launch.
+ *   data:   uint8 [data_bytes] on the device: every image planar [channels][h][w], back to back
+ *   table:  int64 [n][4] on the device: (offset of the image in data, h, w, label); n: 1..DTA_EPOCH_ORDER_MAX_N
+ *   index:  the images of the batch, on the device: int32 (index64 == 0) or int64 [start + count] at least, read at
+ *           start .. start + count - 1 -- so an epoch's order (dta_epoch_order) is read in place --, or NULL: image start + b
+ *   flip:   0 / 1 bytes [count] on the device, per place of the batch, or NULL for none.  hash_flips != 0 (then flip must be
+ *           NULL): image i is flipped where  mix(((epoch * n + i) mod 2^64) * 0x9E3779B97F4A7C15 + mix(seed *
+ *           0x9E3779B97F4A7C15 + DTA_DEAD_FLIP_STREAM + 1)) >> 40  <  2^23: a function of the image, not of its place
+ *   out:    [count][channels][size][size] of `dtype` (DTA_ELEM_*), or [count][size][size][channels] when channels_last != 0:
+ *           place b holds dta_rgb_crops' crop of the whole image (box (0, 0, h, w), pad 0) -- the same arithmetic, the same
+ *           bits --, with its columns reversed where the image is flipped (output column j takes the values of column
+ *           size - 1 - j)
+ *   out_labels: int64 [count]: the images' labels
+ * An index outside 0..n-1 (and a table row that does not lie inside data) gives a crop of zeros and label -1; nothing is
+ * read for it.  At most DTA_RGB_CROPS_MAX_GROUPS workgroups, no workspace, no atomics.  mean, std: HOST arrays of `channels`
+ * floats.  Refused on the host, before any launch: a null data, table, mean, std, out or out_labels, n or data_bytes out
+ * of range, channels outside 1..4, count < 1, start < 0, start + count > n without an index, flip together with hash_flips,
+ * size outside 1..DTA_RGB_CROPS_MAX_SIZE, an unknown dtype, a zero std, a NaN mean or std, an out pointer that is not
+ * aligned to its element (16-byte stores are used where out is 16-byte aligned and the line length allows it). */
+#define DTA_DEAD_FLIP_STREAM 3       /* the hash stream of the flips (csrc/hash_dev.h lists the streams in use) */
+#define DTA_DEAD_ORDER_LEVEL 63      /* the level id dead.ImagePool.loader gives dta_epoch_order: stream 16 + 63 */
+int dta_image_pool_batch(const unsigned char* data, long long data_bytes, const long long* table, long long n, int channels,
+                         const void* index, int index64, long long start, long long count, const unsigned char* flip,
+                         int hash_flips, unsigned long long seed, unsigned long long epoch, int size, const float* mean,
+                         const float* std, int dtype, int channels_last, void* out, long long* out_labels, void* stream);
+/* dta_dead_loss: the loss of one batch, its gradient and the confusion counts in ONE launch of one workgroup.
+ * logits: [rows][2] of `dtype` on the device; labels: int64 [rows].  Per row with a label in {0, 1}, in float32:
+ *   s = 1 / (1 + exp(-l));  m = max(s0, s1);  lse = m + log(exp(s0 - m) + exp(s1 - m));  loss_row = lse - s[y]
+ *   p = exp(s - lse);  d_l[c] = (p[c] - [c == y]) * s[c] * (1 - s[c]) / B_valid
+ * out_loss[0]: the float64 sum of loss_row (per lane in row order, then a fixed tree: a rerun gives the same bits) over
+ * B_valid, rounded to float32 once; 0 where B_valid = 0.  out_dlogits: float32 [rows][2], zeros for the other rows.
+ * out_counts: int64 [5]: conf[label][argmax l, a tie giving 0] as four, then the rows whose label is outside {0, 1}.
+ * accumulator: NULL, or DTA_DEAD_ACC_WORDS 8-byte words on the device that the caller zeroed once: a float64 loss sum,
+ * then int64 rows, conf[2][2], bad; this call's sums are added (launches of one stream follow each other).  No atomics.
+ * Refused before the launch: a null logits, labels, out_loss, out_dlogits or out_counts, rows outside
+ * 1..DTA_DEAD_LOSS_MAX_ROWS, an unknown dtype, an accumulator that is not 8-byte aligned. */
+#define DTA_DEAD_ACC_WORDS 7
+#define DTA_DEAD_LOSS_MAX_ROWS 16777216
+int dta_dead_loss(const void* logits, int dtype, const long long* labels, long long rows, float* out_loss, float* out_dlogits,
+                  long long* out_counts, void* accumulator, void* stream);
+
 /* ---- Reflectance cube to resident raster: the array work of the reference's generate_raster (src/Hyperspectral.py:152-219:
  * band selection, window, transpose to band-first) and of load_image's preprocessing (src/utils.py:36-57) in one pass over a
  * pixel-interleaved cube, as a NEON reflectance tile is stored ([rows][cols][426] int16).  For every pixel of the column
