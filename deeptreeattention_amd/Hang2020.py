@@ -35,6 +35,16 @@ def get_default_precision():
     return _DEFAULT_PRECISION
 
 
+def forward_only_descs(B, bands, Hh, Ww, classes, net_code, precision):
+    """The descriptors of a prediction: the eval-mode forward of the last head that keeps nothing for a backward.  Returns
+    (desc, desc_reuse); the second also takes the weight re-layouts an earlier call left in the workspace as they are
+    (DTA_REUSE_PACKED)."""
+    def desc(reuse):
+        return _lib.NetDesc(B, bands, Hh, Ww, classes, net_code, _lib.dtype_code(precision), 0,
+                            4 | _lib.FORWARD_ONLY | reuse, BN_MOMENTUM, BN_EPS)
+    return desc(0), desc(_lib.REUSE_PACKED)
+
+
 # ----------------------------------------------------------------------------------------------------
 # parameter holders with the reference's names
 # ----------------------------------------------------------------------------------------------------

@@ -79,6 +79,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .Hang2020 import forward_only_descs
 from .preprocess import PatchTiles, out_bands, _DTYPES
 
 WINDOW = 11     # Hang et al. 2020: one 11x11 window per pixel
@@ -603,9 +604,7 @@ class Conv1Table:
         m = pred.nets_mod[0]
         self.height, self.width, self.bands, self.precision, self.device = raster.height, raster.width, raster.bands, raster.precision, raster.device
         self.cols = 64 if m._net_code == _lib.NET_HANG2020 else 32
-        from . import Hang2020 as H
-        self.desc = _lib.NetDesc(1, raster.bands, WINDOW, WINDOW, m._classes, m._net_code, _lib.dtype_code(m.precision), 0,
-                                 4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
+        self.desc = forward_only_descs(1, raster.bands, WINDOW, WINDOW, m._classes, m._net_code, m.precision)[0]
         scratch_b, table_b = _lib.C.c_size_t(), _lib.C.c_size_t()
         _lib.check(L.dta_conv1_table_bytes(_lib.C.byref(self.desc), self.height, self.width, _lib.C.byref(scratch_b),
                                            _lib.C.byref(table_b)), "dta_conv1_table_bytes")
@@ -675,9 +674,7 @@ class Conv1TableYears:
         self.levels, self.years = len(predictor.preds), len(rs)
         self.cols = 32 * self.levels
         self.present = [r is not None for r in rs]
-        from . import Hang2020 as H
-        self.desc = _lib.NetDesc(1, r0.bands, WINDOW, WINDOW, m0._classes, _lib.NET_SPECTRAL, _lib.dtype_code(m0.precision), 0,
-                                 4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
+        self.desc = forward_only_descs(1, r0.bands, WINDOW, WINDOW, m0._classes, _lib.NET_SPECTRAL, m0.precision)[0]
         dt = torch.float16 if self.precision == "bf16" else torch.float32
         size_t = _lib.C.c_size_t
 
@@ -829,8 +826,8 @@ def raster_precision(model_or_predictor):
     return "bf16" if tiles else "fp32"
 
 
-# What the prediction loops gather per batch: windows at origins [N, 2] or resized crops of boxes [N, 4].  The loops
-# (_predict_batches*) are written once and take one of these two.
+# What the prediction loops gather per batch: windows at origins [N, 2] or resized crops of boxes [N, 4].  The routes
+# (_single_route, _metadata_route, _predict_batches_multistage) are written once and take one of these two.
 #   index(raster, items)  the caller's origins / boxes -> the int32 device tensor the gathers take, once, before the loop
 #   one(raster, idx, ...) a batch out of one raster (DenseRaster.windows / .crops)
 #   years                 a batch out of every year's raster in one launch (DenseRaster.windows_years / .crops_years)
@@ -863,7 +860,7 @@ def predict_windows(model_or_predictor, rasters, origins, crown_offsets=None, ba
     forward without its first conv -- no window of the input is ever formed.  Anything it does not cover raises
     RuntimeError before a launch (_share_conv1_refusals).
     Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None)."""
-    return _predict_batches(_WINDOWS, model_or_predictor, rasters, origins, crown_offsets, batch_size, return_probs, share_conv1)
+    return _single_route(_WINDOWS, model_or_predictor, rasters, origins, crown_offsets, batch_size, return_probs, share_conv1)
 
 
 def predict_crops(model_or_predictor, rasters, boxes, batch_size=4096, return_probs=False):
@@ -877,11 +874,42 @@ def predict_crops(model_or_predictor, rasters, boxes, batch_size=4096, return_pr
     There is no share_conv1 here: a resized crop's 3x3 neighbours are not raster neighbours unless the box is exactly
     11x11, so the first conv's output at a crop position is not a function of the raster pixel underneath.
     Returns WindowPredictions(top_idx [N, 2], top_score [N, 2], probs or None, crowns=None): one row per box."""
-    return _predict_batches(_CROPS, model_or_predictor, rasters, boxes, None, batch_size, return_probs, False)
+    return _single_route(_CROPS, model_or_predictor, rasters, boxes, None, batch_size, return_probs, False)
 
 
-def _predict_batches(gather, model_or_predictor, rasters, items, crown_offsets, batch_size, return_probs, share_conv1):
-    """The loop of predict_windows / predict_crops."""
+def _batch_plan(N, batch_size, crown_offsets):
+    """The preamble of every route, before anything is allocated or launched: (the batch size for N items, the crown
+    offsets checked on the host or None)."""
+    B = min(int(batch_size), N)
+    if B < 1:
+        raise ValueError("batch_size must be positive")
+    return B, None if crown_offsets is None else _host_offsets(crown_offsets, N)
+
+
+def _year_buffers(r0, rs, B, size):
+    """One gather buffer of B items per raster of rs, in r0's form."""
+    zeros = r0._batch(B, size, zero=True) if any(r is None for r in rs) else None      # ONE persistent zero batch stands in for every missing year
+    return [zeros if r is None else r0._batch(B, size) for r in rs]
+
+
+def _predict_batches(o, B, crown_offsets, classes, return_probs, batch):
+    """The walk of the single-output routes over the items o [N, 2 or 4] in batches of B: the outputs, the row slices, the
+    crown tail.  batch(n, items, probs or None, top_idx, top_score) launches one batch of n items into the row slices it is
+    handed; nothing here waits for the device."""
+    dev, N = o.device, o.shape[0]
+    keep = return_probs or crown_offsets is not None
+    top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
+    top_score = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
+    for n0 in range(0, N, B):
+        n = min(B, N - n0)
+        batch(n, o[n0:n0 + n], probs[n0:n0 + n] if keep else None, top_idx[n0:n0 + n], top_score[n0:n0 + n])
+    crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
+    return WindowPredictions(top_idx, top_score, probs if return_probs else None, crowns)
+
+
+def _single_route(gather, model_or_predictor, rasters, items, crown_offsets, batch_size, return_probs, share_conv1):
+    """predict_windows / predict_crops: the checks, then _predict_batches with this route's batch."""
     pred = _predictor(model_or_predictor)
     size = WINDOW
     if share_conv1:
@@ -897,35 +925,29 @@ def _predict_batches(gather, model_or_predictor, rasters, items, crown_offsets, 
         rs = [rasters]
     r0 = _check_rasters(rs, want, "this network reads a DenseRaster(..., precision={!r}) (dense.raster_precision)".format(want),
                         one_device=False)[0]
-    dev = r0.device
     o = gather.index(r0, items)
-    L = _lib.lib()
-    N, classes = o.shape[0], pred.nets_mod[0]._classes
-    keep = return_probs or crown_offsets is not None
-    top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
-    top_score = torch.empty(N, 2, dtype=torch.float32, device=dev)
-    probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
-    B = min(int(batch_size), N)
-    tiles = want == "bf16"
+    B, crown_offsets = _batch_plan(o.shape[0], batch_size, crown_offsets)
+    classes = pred.nets_mod[0]._classes
+    L, st = _lib.lib(), _lib.current_stream_ptr()
+
+    def top2(logits, n, probs, top_idx, top_score):
+        _lib.check(L.dta_softmax_top2(_lib.ptr(logits), n, classes, _lib.ptr(probs), _lib.ptr(top_idx), _lib.ptr(top_score), st),
+                   "dta_softmax_top2")
+
     if share_conv1:
         table = r0.conv1_table(pred, size=size)
-    else:
-        zeros = r0._batch(B, size, zero=True) if any(r is None for r in rs) else None      # ONE stands in for every missing year
-        bufs = [zeros if r is None else r0._batch(B, size) for r in rs]
-    st = _lib.current_stream_ptr()
-    for n0 in range(0, N, B):
-        n = min(B, N - n0)
-        ob = o[n0:n0 + n]
-        if share_conv1:
+
+        def batch(n, ob, *out):
             table.gather(ob, pred.conv1_slot(n, r0.bands))
-            logits = pred.logits_from_conv1()
-        else:
+            top2(pred.logits_from_conv1(), n, *out)
+    else:
+        tiles = want == "bf16"
+        bufs = _year_buffers(r0, rs, B, size)
+
+        def batch(n, ob, *out):
             xs = [b[:n] if r is None else gather.one(r, ob, tiles=tiles, size=size, out=b[:n]) for r, b in zip(rs, bufs)]
-            logits = pred.logits_of(xs if pred.ensemble else xs[0])
-        _lib.check(L.dta_softmax_top2(_lib.ptr(logits), n, classes, _lib.ptr(probs[n0:n0 + n]) if keep else None,
-                                      _lib.ptr(top_idx[n0:n0 + n]), _lib.ptr(top_score[n0:n0 + n]), st), "dta_softmax_top2")
-    crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
-    return WindowPredictions(top_idx, top_score, probs if return_probs else None, crowns)
+            top2(pred.logits_of(xs if pred.ensemble else xs[0]), n, *out)
+    return _predict_batches(o, B, crown_offsets, classes, return_probs, batch)
 
 
 def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=None, clip=10, batch_size=4096, share_conv1=False):
@@ -941,13 +963,18 @@ def predict_map(model_or_predictor, raster, anchor="center", rows=None, cols=Non
     def resident(r):
         return r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision=want, device=pred.device)
     rs = [resident(r) for r in raster] if pred.ensemble else resident(raster)
-    first = next(r for r in rs if r is not None) if pred.ensemble else rs
+    origins, hw = _region(next(r for r in rs if r is not None) if pred.ensemble else rs, rows, cols, anchor)
+    res = predict_windows(pred, rs, origins, batch_size=batch_size, share_conv1=share_conv1)
+    return res.top_idx[:, 0].reshape(hw), res.top_score[:, 0].reshape(hw)
+
+
+def _region(first, rows, cols, anchor):
+    """The region of a predict_map*: rows / cols are half-open (start, stop) pixel ranges, by default all of the raster
+    `first`.  Returns (one window origin per pixel, row-major, and the region's (h, w))."""
     r0, r1 = rows if rows is not None else (0, first.height)
     c0, c1 = cols if cols is not None else (0, first.width)
     origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
-    res = predict_windows(pred, rs, origins, batch_size=batch_size, share_conv1=share_conv1)
-    h, w = r1 - r0, c1 - c0
-    return res.top_idx[:, 0].reshape(h, w), res.top_score[:, 0].reshape(h, w)
+    return origins, (r1 - r0, c1 - c0)
 
 
 MultiStageWindowPredictions = collections.namedtuple("MultiStageWindowPredictions",
@@ -1015,8 +1042,7 @@ def _predict_batches_multistage(gather, predictor, rasters, items, crown_offsets
     dev, size, Y = r0.device, WINDOW, len(rs)
     o = gather.index(r0, items)
     N = o.shape[0]
-    if crown_offsets is not None:
-        crown_offsets = _host_offsets(crown_offsets, N)
+    B, crown_offsets = _batch_plan(N, batch_size, crown_offsets)
     classes = [p.nets_mod[0]._classes for p in predictor.preds]
     nl = len(classes)
     keep = return_probs or crown_offsets is not None
@@ -1025,14 +1051,10 @@ def _predict_batches_multistage(gather, predictor, rasters, items, crown_offsets
     top_idx = [torch.empty(N, 2, dtype=torch.int64, device=dev) for _ in range(nl)]
     top_score = [torch.empty(N, 2, dtype=torch.float32, device=dev) for _ in range(nl)]
     probs = [torch.empty(N, c, dtype=torch.float32, device=dev) for c in classes] if keep else None
-    B = min(int(batch_size), N)
-    if B < 1:
-        raise ValueError("batch_size must be positive")
     if share_conv1:
         table = Conv1TableYears(rs, predictor)
     else:
-        zeros = r0._batch(B, size, zero=True) if len(have) < Y else None      # ONE persistent zero batch stands in for every missing year
-        bufs = [zeros if r is None else r0._batch(B, size) for r in rs]
+        bufs = _year_buffers(r0, rs, B, size)
     banks = [torch.zeros(Y, dtype=torch.float32, device=dev) for _ in range(2)]
     bank = 0
     for n0 in range(0, N, B):
@@ -1077,12 +1099,9 @@ def predict_map_multistage(predictor, rasters, anchor="center", rows=None, cols=
     rs = [r if r is None or isinstance(r, DenseRaster) else DenseRaster(r, clip=clip, precision=want, device=predictor.device)
           for r in rs]
     first = (_share_conv1_multistage_refusals(predictor, rs, WINDOW) if share_conv1 else _check_years(rs))[0]
-    r0, r1 = rows if rows is not None else (0, first.height)
-    c0, c1 = cols if cols is not None else (0, first.width)
-    origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
+    origins, hw = _region(first, rows, cols, anchor)
     res = predict_windows_multistage(predictor, rs, origins, batch_size=batch_size, share_conv1=share_conv1)
-    h, w = r1 - r0, c1 - c0
-    return res.ens_label.reshape(h, w), res.ens_score.reshape(h, w), res.ens_level.reshape(h, w)
+    return res.ens_label.reshape(hw), res.ens_score.reshape(hw), res.ens_level.reshape(hw)
 
 
 def predict_windows_metadata(predictor, raster, site, origins, crown_offsets=None, batch_size=4096, return_probs=False):
@@ -1092,7 +1111,7 @@ def predict_windows_metadata(predictor, raster, site, origins, crown_offsets=Non
     device.  predictor: an engine.MetadataPredictor (its table is built once, before the loop).  raster: a DenseRaster in
     the form raster_precision(predictor.sensor) names.  site: the raster's site index, one int.
     Returns WindowPredictions(top_idx, top_score, probs or None, crowns or None) as predict_windows does."""
-    return _predict_batches_metadata(_WINDOWS, predictor, raster, site, origins, crown_offsets, batch_size, return_probs)
+    return _metadata_route(_WINDOWS, predictor, raster, site, origins, crown_offsets, batch_size, return_probs)
 
 
 def predict_crops_metadata(predictor, raster, site, boxes, batch_size=4096, return_probs=False):
@@ -1100,11 +1119,11 @@ def predict_crops_metadata(predictor, raster, site, boxes, batch_size=4096, retu
     loop (the sensor model's eval forward, then dta_meta_predict with the raster's site for every row).  predictor /
     raster / site as for predict_windows_metadata; boxes as for predict_crops.  No share_conv1: see predict_crops.
     Returns WindowPredictions, one row per box, crowns=None."""
-    return _predict_batches_metadata(_CROPS, predictor, raster, site, boxes, None, batch_size, return_probs)
+    return _metadata_route(_CROPS, predictor, raster, site, boxes, None, batch_size, return_probs)
 
 
-def _predict_batches_metadata(gather, predictor, raster, site, items, crown_offsets, batch_size, return_probs):
-    """The loop of predict_windows_metadata / predict_crops_metadata."""
+def _metadata_route(gather, predictor, raster, site, items, crown_offsets, batch_size, return_probs):
+    """predict_windows_metadata / predict_crops_metadata: the checks, then _predict_batches with this route's batch."""
     from .engine import MetadataPredictor
     if not isinstance(predictor, MetadataPredictor):
         raise TypeError("the metadata route needs an engine.MetadataPredictor")
@@ -1117,27 +1136,16 @@ def _predict_batches_metadata(gather, predictor, raster, site, items, crown_offs
     site = int(site)
     if not 0 <= site < predictor.sites:
         raise ValueError("site {} is outside [0, {})".format(site, predictor.sites))
-    dev, size = raster.device, WINDOW
+    size = WINDOW
     o = gather.index(raster, items)
-    N, classes = o.shape[0], predictor.classes
-    if crown_offsets is not None:
-        crown_offsets = _host_offsets(crown_offsets, N)
-    B = min(int(batch_size), N)
-    if B < 1:
-        raise ValueError("batch_size must be positive")
-    keep = return_probs or crown_offsets is not None
-    top_idx = torch.empty(N, 2, dtype=torch.int64, device=dev)
-    top_score = torch.empty(N, 2, dtype=torch.float32, device=dev)
-    probs = torch.empty(N, classes, dtype=torch.float32, device=dev) if keep else None
+    B, crown_offsets = _batch_plan(o.shape[0], batch_size, crown_offsets)
     buf = raster._batch(B, size)
     ws = predictor.table()
-    for n0 in range(0, N, B):
-        n = min(B, N - n0)
-        x = gather.one(raster, o[n0:n0 + n], tiles=want == "bf16", size=size, out=buf[:n])
-        scores = sens.logits_of(x)
-        predictor.head(scores, n, ws, site, None, probs[n0:n0 + n] if keep else None, top_idx[n0:n0 + n], top_score[n0:n0 + n])
-    crowns = crown_reduce(probs, crown_offsets) if crown_offsets is not None else None
-    return WindowPredictions(top_idx, top_score, probs if return_probs else None, crowns)
+
+    def batch(n, ob, *out):
+        x = gather.one(raster, ob, tiles=want == "bf16", size=size, out=buf[:n])
+        predictor.head(sens.logits_of(x), n, ws, site, None, *out)
+    return _predict_batches(o, B, crown_offsets, predictor.classes, return_probs, batch)
 
 
 def predict_map_metadata(predictor, raster, site, anchor="center", rows=None, cols=None, clip=10, batch_size=4096):
@@ -1148,9 +1156,6 @@ def predict_map_metadata(predictor, raster, site, anchor="center", rows=None, co
         raise TypeError("the metadata route needs an engine.MetadataPredictor")
     if not isinstance(raster, DenseRaster):
         raster = DenseRaster(raster, clip=clip, precision=raster_precision(predictor.sensor), device=predictor.device)
-    r0, r1 = rows if rows is not None else (0, raster.height)
-    c0, c1 = cols if cols is not None else (0, raster.width)
-    origins, _ = window_origins([(r0, c0, r1, c1)], anchor=anchor, size=WINDOW)
+    origins, hw = _region(raster, rows, cols, anchor)
     res = predict_windows_metadata(predictor, raster, site, origins, batch_size=batch_size)
-    h, w = r1 - r0, c1 - c0
-    return res.top_idx[:, 0].reshape(h, w), res.top_score[:, 0].reshape(h, w)
+    return res.top_idx[:, 0].reshape(hw), res.top_score[:, 0].reshape(hw)

@@ -2056,16 +2056,14 @@ class Predictor:
             return
         B, bands, Hh, Ww = shape
         single = m0._net_code in (_lib.NET_HANG2020, _lib.NET_VANILLA)
-        self.desc = _lib.NetDesc(B, bands, Hh, Ww, m0._classes, m0._net_code, _lib.dtype_code(m0.precision), 0,
-                                 4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
-        self.desc_reuse = _lib.NetDesc(B, bands, Hh, Ww, m0._classes, m0._net_code, _lib.dtype_code(m0.precision), 0,
-                                       4 | _lib.FORWARD_ONLY | _lib.REUSE_PACKED, H.BN_MOMENTUM, H.BN_EPS)
+        self.desc, self.desc_reuse = H.forward_only_descs(B, bands, Hh, Ww, m0._classes, m0._net_code, m0.precision)
         self._packed = False
         self._packed_conv1 = False
         tables = self._tables([nets_mod[i] for i in kept])
         if self.ensemble:
             self.nets = (_lib.SubnetParams * len(kept))(*[t[0] for t in tables])
             nbytes = L.dta_ensemble_workspace_bytes(C.byref(self.desc), len(kept))
+            self._banks, self._bank = _flag_banks(len(kept), self.device), 0
         else:
             self.nets = tables[0]
             nbytes = L.dta_net_workspace_bytes(C.byref(self.desc))
@@ -2088,13 +2086,8 @@ class Predictor:
             xs = [H._check_input(x) for x in images]
             kept = list(range(len(xs)))
             self._prepare(xs[0].shape, kept)
-            if getattr(self, "_banks", None) is None or self._banks[0].numel() != len(xs):
-                # two flag banks: a call writes one and zeroes the other for the next call (no clearing launch)
-                self._banks = [torch.zeros(len(xs), dtype=torch.float32, device=self.device) for _ in range(2)]
-                self._bank = 0
             flags, nxt = self._banks[self._bank], self._banks[self._bank ^ 1]
             self._bank ^= 1
-            self._flags = flags
             xptr = (C.c_void_p * len(kept))(*[x.data_ptr() for x in xs])
             _lib.check(L.dta_year_flags(xptr, len(xs), xs[0].numel(), _lib.ptr(flags), _lib.ptr(nxt), st), "dta_year_flags")
             _lib.check(L.dta_ensemble_forward_gated(C.byref(self._desc()), len(kept), self.nets, xptr, _lib.ptr(flags),
@@ -2124,6 +2117,16 @@ class Predictor:
         else:
             x = H._check_input(images)
         self._prepare(x.shape, [0])
+        alpha, table, joint = self._single_args()
+        fwd = L.dta_net_forward if tiles is None else L.dta_net_forward_tiles
+        _lib.check(fwd(C.byref(self._desc()), self.nets, alpha, _lib.ptr(x if tiles is None else tiles), _lib.ptr(self.ws),
+                       C.byref(table), joint, st), "dta_net_forward" if tiles is None else "dta_net_forward_tiles")
+        self._packed = True
+        return self.logits
+
+    def _single_args(self):
+        """(alpha, score table, joint scores) of the single-network forwards: self.logits receives the joint scores of a
+        Hang2020 / vanilla_CNN, the last head's of a lone branch network."""
         m = self.nets_mod[0]
         table = _lib.ScoreTable()
         joint = _lib.ptr(self.logits)
@@ -2131,11 +2134,7 @@ class Predictor:
             table[0][2] = self.logits.data_ptr()
             joint = None
         alpha = _lib.ptr(m.alpha) if m._net_code == _lib.NET_HANG2020 else None
-        fwd = L.dta_net_forward if tiles is None else L.dta_net_forward_tiles
-        _lib.check(fwd(C.byref(self._desc()), self.nets, alpha, _lib.ptr(x if tiles is None else tiles), _lib.ptr(self.ws),
-                       C.byref(table), joint, st), "dta_net_forward" if tiles is None else "dta_net_forward_tiles")
-        self._packed = True
-        return self.logits
+        return alpha, table, joint
 
     def conv1_slot(self, n, bands):
         """The place of the first conv's output inside this Predictor's workspace for a batch of n 11x11 windows (the
@@ -2153,13 +2152,7 @@ class Predictor:
         dta_gather_conv1_windows): the forward without its first conv (dta_conv1_forward).  The returned tensor is reused
         by the next call."""
         L = _lib.lib()
-        m = self.nets_mod[0]
-        table = _lib.ScoreTable()
-        joint = _lib.ptr(self.logits)
-        if not self.single:
-            table[0][2] = self.logits.data_ptr()
-            joint = None
-        alpha = _lib.ptr(m.alpha) if m._net_code == _lib.NET_HANG2020 else None
+        alpha, table, joint = self._single_args()
         # frozen weights: this call leaves every re-layout but the first layer's row table behind, so it may reuse what a
         # call of either kind packed, while the full forward (logits_of) reuses only what a full forward packed
         reuse = self.frozen and (self._packed or self._packed_conv1)
@@ -2337,10 +2330,7 @@ class MultiStagePredictor:
         if any(m.precision != m0.precision for ms in mods for m in ms):
             raise ValueError("all levels must run in the same precision")
         B, bands, Hh, Ww = shape
-        self.desc = _lib.NetDesc(B, bands, Hh, Ww, m0._classes, _lib.NET_SPECTRAL, _lib.dtype_code(m0.precision), 0,
-                                 4 | _lib.FORWARD_ONLY, H.BN_MOMENTUM, H.BN_EPS)
-        self.desc_reuse = _lib.NetDesc(B, bands, Hh, Ww, m0._classes, _lib.NET_SPECTRAL, _lib.dtype_code(m0.precision), 0,
-                                       4 | _lib.FORWARD_ONLY | _lib.REUSE_PACKED, H.BN_MOMENTUM, H.BN_EPS)
+        self.desc, self.desc_reuse = H.forward_only_descs(B, bands, Hh, Ww, m0._classes, _lib.NET_SPECTRAL, m0.precision)
         self._packed = False
         self._packed_conv1 = False
         nets, lv = [], []
@@ -2364,9 +2354,7 @@ class MultiStagePredictor:
         if nbytes == 0:
             raise RuntimeError("dta_multistage_workspace_bytes: " + L.dta_last_error().decode())
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        # two flag banks: a call writes one and zeroes the other for the next call (no clearing launch)
-        self._banks = [torch.zeros(len(self.preds[0].nets_mod), dtype=torch.float32, device=self.device) for _ in range(2)]
-        self._bank = 0
+        self._banks, self._bank = _flag_banks(len(self.preds[0].nets_mod), self.device), 0
         self._key = key
 
     def __call__(self, images, return_probs=True, present=None, year_flags=None):
@@ -2383,6 +2371,12 @@ class MultiStagePredictor:
         labels): the call also counts into `self.confusion` (rows = label, columns = prediction; zero it to start a new
         epoch).  The call's per-level outputs are in self.probs / self.top_idx / self.top_score as after __call__
         (`per_level()` hands them back as __call__'s triples).  year_flags: as __call__'s."""
+        self._run(images, return_probs, present, self._ensemble_setup(labels), year_flags)
+        return self._ens
+
+    def _ensemble_setup(self, labels):
+        """What ensemble / ensemble_from_conv1 check and create before their chain: the hierarchy against the levels, the
+        labels on the device, the confusion matrix of the first labelled call.  Returns the chain's `ens` argument."""
         if self.hierarchy is None:
             raise RuntimeError("MultiStagePredictor.ensemble needs a hierarchy (MultiStagePredictor(models, hierarchy=...))")
         if self.hierarchy.levels != len(self.preds):
@@ -2391,8 +2385,7 @@ class MultiStagePredictor:
             labels = _species_labels(labels, self.device)
             if self.confusion is None:
                 self.confusion = torch.zeros(self.hierarchy.n_species, self.hierarchy.n_species, dtype=torch.int64, device=self.device)
-        self._run(images, return_probs, present, (labels,), year_flags)
-        return self._ens
+        return (labels,)
 
     def per_level(self, return_probs=True):
         """The last call's (probs or None, top_idx, top_score) triple per level."""
@@ -2423,52 +2416,24 @@ class MultiStagePredictor:
 
     def ensemble_from_conv1(self, year_flags, labels=None, return_probs=True):
         """ensemble() for such a batch (dta_conv1_multistage_predict_ensemble)."""
-        if self.hierarchy is None:
-            raise RuntimeError("MultiStagePredictor.ensemble needs a hierarchy (MultiStagePredictor(models, hierarchy=...))")
-        if self.hierarchy.levels != len(self.preds):
-            raise ValueError("the hierarchy has {} levels, the predictor {}".format(self.hierarchy.levels, len(self.preds)))
-        if labels is not None:
-            labels = _species_labels(labels, self.device)
-            if self.confusion is None:
-                self.confusion = torch.zeros(self.hierarchy.n_species, self.hierarchy.n_species, dtype=torch.int64, device=self.device)
-        self._run_conv1(return_probs, (labels,), year_flags)
+        self._run_conv1(return_probs, self._ensemble_setup(labels), year_flags)
         return self._ens
 
-    def _run_conv1(self, return_probs, ens, year_flags):
-        L = _lib.lib()
-        st = _lib.current_stream_ptr()
-        nl = len(self.preds)
-        Y = len(self.preds[0].nets_mod)
-        if self._key is None or tuple(self._key[0][2:]) != (11, 11) or len(self._key[2]) != Y:
-            raise RuntimeError("no first-conv output in the workspace: fill conv1_slot() first")
+    def _check_year_flags(self, year_flags, Y):
         if (not isinstance(year_flags, torch.Tensor) or year_flags.dtype != torch.float32 or tuple(year_flags.shape) != (Y,)
                 or year_flags.device != self.device):
             raise ValueError("year_flags must be a float32 [{}] tensor on {}".format(Y, self.device))
-        gate = year_flags.repeat(nl)                # the (level, year) groups' flags: the years' flags once per level
-        # frozen weights: these calls leave every re-layout but the first layer's row table behind, so they may reuse what a
-        # call of either kind packed, while the full forward (_run) reuses only what a full forward packed
-        reuse = self.frozen and (self._packed or self._packed_conv1)
-        desc = self.desc_reuse if reuse else self.desc
-        if ens is None:
-            _lib.check(L.dta_conv1_multistage_predict(C.byref(desc), nl, self.lv, self.nets, _lib.ptr(gate), _lib.ptr(self.ws),
-                                                      self._pp if return_probs else None, self._pi, self._ps, st),
-                       "dta_conv1_multistage_predict")
-        else:
-            labels, = ens
-            B = self._key[0][0]
-            if labels is not None and labels.shape[0] != B:
-                raise ValueError("one species label per crop")
-            if self._ens is None or self._ens[0].shape[0] != B:
-                self._ens = _ensemble_buffers(B, self.device)
-            table = self.hierarchy.c_table(self.device)
-            _lib.check(L.dta_conv1_multistage_predict_ensemble(C.byref(desc), nl, self.lv, self.nets, _lib.ptr(gate), _lib.ptr(self.ws),
-                                                               self._pp if return_probs else None, self._pi, self._ps, C.byref(table),
-                                                               _lib.ptr(self._ens[0]), _lib.ptr(self._ens[1]), _lib.ptr(self._ens[2]),
-                                                               _lib.ptr(labels), _lib.ptr(self.confusion if labels is not None else None), st),
-                       "dta_conv1_multistage_predict_ensemble")
-        self._packed_conv1 = True
-        self._live = (labels if ens is not None else None, gate)
-        return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(nl)]
+
+    def _run_conv1(self, return_probs, ens, year_flags):
+        st = _lib.current_stream_ptr()
+        Y = len(self.preds[0].nets_mod)
+        if self._key is None or tuple(self._key[0][2:]) != (11, 11) or len(self._key[2]) != Y:
+            raise RuntimeError("no first-conv output in the workspace: fill conv1_slot() first")
+        self._check_year_flags(year_flags, Y)
+        gate = year_flags.repeat(len(self.preds))   # the (level, year) groups' flags: the years' flags once per level
+        out = self._launch(True, None, gate, return_probs, ens, st)
+        self._live = (ens[0] if ens is not None else None, gate)
+        return out
 
     def _run(self, images, return_probs, present, ens, year_flags=None):
         L = _lib.lib()
@@ -2478,9 +2443,7 @@ class MultiStagePredictor:
         if year_flags is not None:
             if present is not None:
                 raise ValueError("pass `present` (host booleans) or `year_flags` (device flags), not both")
-            if (not isinstance(year_flags, torch.Tensor) or year_flags.dtype != torch.float32 or tuple(year_flags.shape) != (Y,)
-                    or year_flags.device != self.device):
-                raise ValueError("year_flags must be a float32 [{}] tensor on {}".format(Y, self.device))
+            self._check_year_flags(year_flags, Y)
         if present is None:
             kept = list(range(Y))
         else:
@@ -2501,29 +2464,44 @@ class MultiStagePredictor:
             self._bank ^= 1
             _lib.check(L.dta_year_flags(yptr, Y, xs[0].numel(), _lib.ptr(flags), _lib.ptr(nxt), st), "dta_year_flags")
             gate = flags.repeat(nl)                 # the (level, year) groups' flags: the years' flags once per level
-        # forward of all levels x years + ONE launch for every level's mean over its years, softmax and top-2
-        desc = self.desc_reuse if (self.frozen and self._packed) else self.desc
-        if ens is None:
-            _lib.check(L.dta_multistage_predict(C.byref(desc), nl, self.lv, self.nets, xptr, _lib.ptr(gate), _lib.ptr(self.ws),
-                                                self._pp if return_probs else None, self._pi, self._ps, st), "dta_multistage_predict")
-        else:
-            # ... and the walk down the hierarchy (and the confusion count) in that same launch
+        out = self._launch(False, xptr, gate, return_probs, ens, st)
+        self._live = (xs if ens is None else (xs, ens[0]), gate)
+        return out
+
+    def _launch(self, conv1, xptr, gate, return_probs, ens, st):
+        """The launch tail of _run (the full forward, on xptr) and _run_conv1 (conv1: the forward behind the first convs that
+        are in the workspace; no xptr): the forward of all levels x years + ONE launch for every level's mean over its years,
+        softmax and top-2 -- with `ens` also the walk down the hierarchy (and the confusion count) in that same launch.
+        Returns the per-level triples."""
+        nl = len(self.preds)
+        # frozen weights: the conv1 forward leaves every re-layout but the first layer's row table behind, so it may reuse what
+        # a call of either kind packed, while the full forward reuses only what a full forward packed
+        reuse = self.frozen and (self._packed or (conv1 and self._packed_conv1))
+        entry = "dta_conv1_multistage_predict" if conv1 else "dta_multistage_predict"
+        args = (C.byref(self.desc_reuse if reuse else self.desc), nl, self.lv, self.nets) + (() if conv1 else (xptr,)) + (
+            _lib.ptr(gate), _lib.ptr(self.ws), self._pp if return_probs else None, self._pi, self._ps)
+        if ens is not None:
             labels, = ens
-            B = xs[0].shape[0]
+            B = self._key[0][0]
             if labels is not None and labels.shape[0] != B:
                 raise ValueError("one species label per crop")
             if self._ens is None or self._ens[0].shape[0] != B:
                 self._ens = _ensemble_buffers(B, self.device)
             table = self.hierarchy.c_table(self.device)
-            _lib.check(L.dta_multistage_predict_ensemble(C.byref(desc), nl, self.lv, self.nets, xptr, _lib.ptr(gate), _lib.ptr(self.ws),
-                                                         self._pp if return_probs else None, self._pi, self._ps, C.byref(table),
-                                                         _lib.ptr(self._ens[0]), _lib.ptr(self._ens[1]), _lib.ptr(self._ens[2]),
-                                                         _lib.ptr(labels), _lib.ptr(self.confusion if labels is not None else None), st),
-                       "dta_multistage_predict_ensemble")
-            xs = (xs, labels)
-        self._packed = True
-        self._live = (xs, gate)
-        return [(self.probs[l] if return_probs else None, self.top_idx[l], self.top_score[l]) for l in range(nl)]
+            entry += "_ensemble"
+            args += (C.byref(table), _lib.ptr(self._ens[0]), _lib.ptr(self._ens[1]), _lib.ptr(self._ens[2]),
+                     _lib.ptr(labels), _lib.ptr(self.confusion if labels is not None else None))
+        _lib.check(getattr(_lib.lib(), entry)(*args, st), entry)
+        if conv1:
+            self._packed_conv1 = True
+        else:
+            self._packed = True
+        return self.per_level(return_probs)
+
+
+def _flag_banks(years, device):
+    """The two banks of the years' flags: a call writes one and zeroes the other for the next call (no clearing launch)."""
+    return [torch.zeros(years, dtype=torch.float32, device=device) for _ in range(2)]
 
 
 def _ensemble_buffers(B, device):

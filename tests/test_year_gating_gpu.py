@@ -34,7 +34,8 @@ def test_year_flags_kernel():
     ptrs = (C.c_void_p * 4)(*[x.data_ptr() for x in xs])
     _lib.check(L.dta_year_flags(ptrs, 4, n, _lib.ptr(flags), None, _lib.current_stream_ptr()), "dta_year_flags")
     assert flags.tolist() == [0.0, 1.0, 1.0, 0.0]
-    assert L.dta_year_flags(ptrs, 9, n, _lib.ptr(flags), None, None) != 0          # more years than a grouped launch takes
+    # more years than a grouped launch takes (_lib.MAX_YEARS): refused on the count, before a pointer of the 4-entry array is read
+    assert L.dta_year_flags(ptrs, _lib.MAX_YEARS + 1, n, _lib.ptr(flags), None, None) != 0
 
 
 def _images(step, zero=()):
