@@ -46,6 +46,11 @@ The package mirrors the reference's module names for this path only:
                                      device (one launch per batch) and reduced in one launch -- per-site micro / macro,
                                      per-species accuracy / precision, the within-site and within-genus shares of the
                                      errors -- plus the first row per individual and the novel-species scores
+    deeptreeattention_amd.mosaic     <->  src/predict.py predict_crowns + src/generate.py predict_trees (DeepForest's predict_tile
+                                     around a stock detector): the window layout, the shift of every window's boxes to
+                                     tile coordinates, the exact greedy non-maximum suppression over the whole tile (binned
+                                     by cells, decided in parallel rounds, no sort) and the pixel boxes every module above
+                                     takes
     deeptreeattention_amd.loop       epoch loops: fit / fit_multistage, validate / validate_multistage (validation with the
                                      metric counts taken on the device), predict_multistage
 All arithmetic runs in libdta_hip.so (HIP, C ABI in include/dta_hip.h); there is no CPU fallback.

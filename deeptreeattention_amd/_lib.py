@@ -133,6 +133,16 @@ FIELD_REASON_BAD_CODE = 255
 MEGAPLOT_GRID, MEGAPLOT_BUFFER = 0, 1
 MEGAPLOT_BUFFER_MAX = 65536   # DTA_MEGAPLOT_BUFFER_MAX
 MEGAPLOT_CHUNK = 1024   # DTA_MEGAPLOT_CHUNK
+# DTA_MOSAIC_* status codes and constants
+MOSAIC_DROPPED, MOSAIC_KEPT, MOSAIC_MASKED, MOSAIC_REFUSED, MOSAIC_UNDECIDED = 0, 1, 2, 3, 4
+MOSAIC_CHUNK = 1024   # DTA_MOSAIC_CHUNK
+MOSAIC_ROUNDS = 12  # DTA_MOSAIC_ROUNDS
+MOSAIC_MAX_ROUNDS = 64   # DTA_MOSAIC_MAX_ROUNDS
+
+
+class MosaicOptions(C.Structure):   # dta_mosaic_options
+    _fields_ = [("height", C.c_int), ("width", C.c_int), ("n_windows", C.c_int), ("max_side", C.c_float),
+                ("iou_threshold", C.c_float), ("rounds", C.c_int), ("no_tail", C.c_int)]
 
 
 class LevelTables(C.Structure):     # dta_level_tables
@@ -486,6 +496,14 @@ def lib():
         L.dta_first_rows.argtypes = [vp, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp]
         L.dta_novel_scores.restype = C.c_int
         L.dta_novel_scores.argtypes = [vp, C.c_longlong, C.c_int, vp, vp, vp, vp]
+        # crown boxes from detector windows: shift, exact greedy NMS by cells and rounds, pixel boxes (mosaic.hip)
+        L.dta_mosaic_workspace_bytes.restype = C.c_size_t
+        L.dta_mosaic_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_float]
+        L.dta_mosaic_grid.restype = C.c_int
+        L.dta_mosaic_grid.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int)]
+        L.dta_mosaic.restype = C.c_int
+        L.dta_mosaic.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.POINTER(MosaicOptions), vp, vp, vp, vp, vp, C.c_size_t, vp]
         L.dta_profile_enable.restype = C.c_int
         L.dta_profile_enable.argtypes = [C.c_int]
         L.dta_profile_set_stride.restype = C.c_int

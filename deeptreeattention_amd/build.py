@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["conv.hip", "conv_bf16.hip", "stage.hip", "heads.hip", "capi.hip", "capi_modules.hip", "preprocess.hip", "xchg.hip", "meta.hip", "dense.hip", "dense_conv1.hip", "abundance.hip", "abundance_grid.hip", "canopy.hip", "dead.hip", "dead_train.hip", "reflectance.hip", "stems.hip", "split.hip", "treedata.hip", "levels.hip", "field.hip", "evaluate.hip", "boundary.hip"]
+SOURCES = ["conv.hip", "conv_bf16.hip", "stage.hip", "heads.hip", "capi.hip", "capi_modules.hip", "preprocess.hip", "xchg.hip", "meta.hip", "dense.hip", "dense_conv1.hip", "abundance.hip", "abundance_grid.hip", "canopy.hip", "dead.hip", "dead_train.hip", "reflectance.hip", "stems.hip", "split.hip", "treedata.hip", "levels.hip", "field.hip", "evaluate.hip", "mosaic.hip", "boundary.hip"]
 # every header of csrc/ and the public one, taken from the directory: a new header cannot be forgotten (an unlisted one
 # triggers no rebuild when edited and stays out of dta_build_id)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "dta_hip.h")]

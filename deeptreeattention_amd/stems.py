@@ -44,7 +44,8 @@ keep = (status == 1) | (status == 2) is a mask in the sense of canopy's `keep`.
 assign_np is the definition; CrownBoxes.assign equals it bit for bit.  The device compares a stem with the boxes and the
 stems of the plots its workgroup of 256 stems touches: N x (boxes + stems of a plot) in all, linear in practice because
 plots are 40 m cells, and quadratic in the stems of one plot if a caller makes a whole tile one plot.
-Out of scope: DeepForest itself, reading rasters or shapefiles, rasterio.windows.from_bounds (a caller keeps its own pixel
+Out of scope: DeepForest itself (what sits between its detector's per-window output and these boxes -- the window layout, the
+shift, the non-maximum suppression, the pixel boxes -- is mosaic.py), reading rasters or shapefiles, rasterio.windows.from_bounds (a caller keeps its own pixel
 boxes and indexes them with `box`), crown polygons other than boxes.  The `point_plot` codes of a contributed megaplot
 (the grid and the buffers of src/megaplot.py) come from field.megaplot_plots.
 """

@@ -1373,6 +1373,63 @@ int dta_first_rows(const void* ids, int ids_is_64, long long rows, long long n_i
 int dta_novel_scores(const float* logits, long long rows, int classes, long long* label_out, float* top_out,
                      float* softmax_out, void* stream);
 
+/* ---- Crown boxes of a tile from a detector's per-window output: the shift by the window origin and the greedy
+ * non-maximum suppression of DeepForest's predict_tile (the reference's predict_crowns, src/predict.py:112-138, and
+ * predict_trees, src/generate.py:17-60).  deeptreeattention_amd/mosaic.py: nms_np and pixel_boxes_np are the definition (they
+ * state the rule in full) and the kernels equal them bit for bit.  All arrays on the device.
+ *
+ * boxes: float [n][4] (xmin, ymin, xmax, ymax) in window pixels; scores: float [n]; window: int [n], the row of origins:
+ * int [n_windows][2] (x, y), |value| < 2^24 (both NULL: the boxes are tile coordinates already); mask: unsigned char [n] or
+ * NULL.  Outputs, every element of the n rows written and nothing behind them:
+ *   boxes_out        float [n][4]  box + (ox, oy, ox, oy), float32 adds; unshifted for a window index out of range
+ *   status_out       unsigned char [n]  DTA_MOSAIC_REFUSED: a coordinate of boxes_out or the score is not finite, xmax < xmin
+ *                    or ymax < ymin, a side above max_side, a window index out of range; DTA_MOSAIC_MASKED: mask[i] == 0;
+ *                    else DTA_MOSAIC_KEPT / DTA_MOSAIC_DROPPED by the greedy rule: j precedes i when score[j] > score[i], or
+ *                    the scores are equal and j < i; j suppresses a later i when inter / ((area_i + area_j) - inter) >
+ *                    iou_threshold in float32, each operation rounded on its own, the division correctly rounded
+ *   winner_out       int [n]  a dropped box: the first kept box in the order that suppresses it; a kept box: itself; else -1
+ *   pixel_boxes_out  int [n][4]  (row0, col0, row1, col1) = floor(ymin), floor(xmin), ceil(ymax), ceil(xmax) of boxes_out,
+ *                    each clamped to 0 .. height / width; zeros for a row with a coordinate that is not finite or xmax < xmin
+ *                    or ymax < ymin
+ * The boxes that take part are binned by centre into square cells (counting sort: integer atomics for the counts and the
+ * fill cursor only; the order inside a cell varies between runs and nothing depends on it).  The cell side is max_side plus
+ * one pixel (or plus max_side / 1024 if that is more), doubled until there are no more cells than max(n, 64) and 2^20: two
+ * boxes that overlap have centres less than max_side apart, and the float32 centre and its float32 quotient by the side are
+ * together off by less than a quarter pixel for a tile of at most 2^20 pixels a side, so they lie in adjacent cells.
+ * dta_mosaic_grid reports the plan.  Then `rounds` launches (negative: DTA_MOSAIC_ROUNDS) in which every undecided box looks
+ * at the 3 x 3 cells around its own: dropped as soon as a preceding overlapping box is kept, kept as soon as all of them are
+ * dropped (the first two by cells, DTA_MOSAIC_CHUNK boxes staged through LDS at a time; the later ones over the list of the
+ * boxes the round before left undecided, one wave per box); one launch of a single workgroup that finishes what is
+ * still undecided (at most one pass per undecided box, workgroup barriers only; no_tail != 0 leaves it out and such boxes
+ * keep DTA_MOSAIC_UNDECIDED: for measurements); one launch for the winners.  rounds + 5 launches and one memset on the
+ * stream, no allocation, no host synchronisation; reruns are bit-identical.
+ * workspace: dta_mosaic_workspace_bytes(n, height, width, max_side) bytes, 16-byte aligned (0: an argument out of range).
+ * Refused on the host, before a launch: a null pointer other than window / origins / mask; window without origins or the
+ * reverse; n outside 1 .. 2^30; height or width outside 1 .. 2^20; max_side outside (0, 2^20]; iou_threshold outside
+ * [0, 1]; rounds above DTA_MOSAIC_MAX_ROUNDS; boxes, boxes_out or pixel_boxes_out not 16-byte aligned; a workspace that is
+ * too small or misaligned. */
+#define DTA_MOSAIC_DROPPED 0
+#define DTA_MOSAIC_KEPT 1
+#define DTA_MOSAIC_MASKED 2
+#define DTA_MOSAIC_REFUSED 3
+#define DTA_MOSAIC_UNDECIDED 4
+#define DTA_MOSAIC_CHUNK 1024               /* boxes staged through LDS at a time */
+#define DTA_MOSAIC_ROUNDS 12                /* parallel rounds in front of the tail launch (profiles/README.md) */
+#define DTA_MOSAIC_MAX_ROUNDS 64
+typedef struct {
+  int height, width;            /* the tile, pixels */
+  int n_windows;                /* rows of origins (ignored without a window table) */
+  float max_side;               /* no box is wider or taller: the detector's window */
+  float iou_threshold;
+  int rounds;                   /* parallel rounds; negative: DTA_MOSAIC_ROUNDS */
+  int no_tail;                  /* 0; 1 leaves the tail launch out (measurements) */
+} dta_mosaic_options;
+size_t dta_mosaic_workspace_bytes(long long n, int height, int width, float max_side);
+int dta_mosaic_grid(long long n, int height, int width, float max_side, float* cell, int* gx, int* gy);
+int dta_mosaic(const float* boxes, const float* scores, const int* window, const int* origins, const unsigned char* mask,
+               long long n, const dta_mosaic_options* opt, unsigned char* status_out, int* winner_out, float* boxes_out,
+               int* pixel_boxes_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
